@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- f-gram embed throughput on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (n-gram match -> INT8 row gather -> dequantise ->
 mean -> + wte + wpe -> fp16 store; `scone_embed`) over one batch of B x T synthetic tokens
@@ -14,6 +14,12 @@ tokens -- every rank holds the table and embeds its own batch; no data-path coll
 --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or as plain `python bench.py --gpus N`,
 which starts the N ranks itself (fresh child processes, before this process touches a GPU) and
 fails unless the line it forwards says n_gpus == N.
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure, its `roofline` block (taken from
+the timed steps themselves) and the workload's description.  `--full` adds everything else the record can hold -- the blocks
+below that take runs of their own (`roofline.same_batch` / `hbm_variant` / `mall_variant`, `cpu_baseline`, `latency`,
+`configs`, `sharded`).  `--dump-outputs DIR` writes what the last timed step returned (a fixed, seeded sample of its token
+positions) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), at most 6000 characters (`compact_record`: the driver keeps
 the tail of stdout); the whole record -- every workload description, provenance string and phase split -- is written to the file
@@ -127,8 +133,13 @@ def parse(argv=None):
     ap.add_argument("--no-hbm-variant", action="store_true", help="skip the cache-defeating variant behind roofline.hbm_variant")
     ap.add_argument("--no-sharded-record", action="store_true",
                     help="skip the `sharded` sub-record (N > 1: C5-shaped row-sharded run; N = 1: pinned-host baseline)")
-    ap.add_argument("--quick", action="store_true", help="headline measurement only (A/B tools): no cpu baseline, no "
-                    "hbm variant, no sharded record")
+    ap.add_argument("--quick", action="store_true", help="headline measurement only, even with --full (A/B tools): no cpu "
+                    "baseline, no hbm variant, no sharded record")
+    ap.add_argument("--full", action="store_true", help="measure everything the record can hold, not only the headline: the "
+                    "same-batch contrast, the cache-defeating variants, the cpu baseline and oracle check, the latency grid, the "
+                    "other BASELINE configs and the sharded / pinned-host record (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one returned "
+                    "(float32, a fixed seeded sample of its token positions, <= 48 MiB) and the sample's positions as DIR/*.npy")
     ap.add_argument("--sharded-rows-per-rank", type=int, default=125_000_000,
                     help="sharded record: table rows per rank (C5: 1e9 rows over 8 GPUs)")
     ap.add_argument("--sharded-steps", type=int, default=5)
@@ -144,7 +155,9 @@ def parse(argv=None):
                     help="limit in seconds for one stage of the sharded record (one exchange with its collectives)")
     ap.add_argument("--selftest", default="", choices=["", "hang", "ok"], help=argparse.SUPPRESS)   # CPU rehearsal of the watchdog
     a = ap.parse_args(argv)
-    if a.quick:
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.quick or not a.full:
         a.no_cpu_baseline = a.no_hbm_variant = a.no_sharded_record = a.no_configs = a.no_latency = True
     return a
 
@@ -342,6 +355,25 @@ def c1_oracle_leg(keys, lens, table, tok_np, gpu_out, seconds):
     return {"gpu_vs_oracle_bit_exact": exact, "gpu_vs_oracle_max_rel_err": err, "gpu_vs_oracle_tokens": int(tok_np.size),
             "cpu_port_1core_tokens_per_s": done * tok_np.shape[1] / dt,
             "cpu_port_sample": f"{done} sequences x {tok_np.shape[1]} tokens ({dt:.1f} s; oracle/ref_port.py aggregate(), 1 core)"}
+
+
+DUMP_SEED = 20261016
+DUMP_BYTES = 48 * 2**20
+
+
+def dump_outputs(path, out, d):
+    """--dump-outputs: the rows of `out` (what the last timed step returned, [..., d]) at a fixed, seeded sample of its token
+    positions -- at most DUMP_BYTES of float32 -- as `embeddings.npy`, and those positions (flat token index, float64) as
+    `embeddings_token_index.npy`.  The same arguments give the same inputs and so the same sample in every run."""
+    import numpy as np
+    import torch
+    flat = out.reshape(-1, d)
+    n = min(flat.shape[0], DUMP_BYTES // (4 * d))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.shape[0], size=n, replace=False))
+    rows = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "embeddings.npy"), rows)
+    np.save(os.path.join(path, "embeddings_token_index.npy"), idx.astype(np.float64))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -542,6 +574,8 @@ def main():
     fmt = format_code(args.format)
     bytes_per_launch, bytes_compulsory, sum_k, k_hist, n_rows_distinct, n_tok_distinct = workload_bytes(table, tok, fmt, d)
 
+    last = [out]                      # what the last step returned (--dump-outputs)
+
     def step():
         if emu is not None:
             # this shard's local work only: partial sums over owned rows, then finalise 1/W of the tokens
@@ -551,8 +585,12 @@ def main():
             b0 = min(a0 + per, ntok)
             table.finalize(partial[a0:b0], counts[a0:b0], tok, a0, b0, wte=wte, wpe=wpe, out_dtype=torch.float16,
                            out=out.view(-1, d)[a0:b0])
+            if args.dump_outputs:
+                last[0] = out.view(-1, d)[a0:b0]
         else:
-            cache.embed_tokens(tok, wte=wte, wpe=wpe, exchange=args.exchange, gather_output=not args.no_gather_output)
+            r = cache.embed_tokens(tok, wte=wte, wpe=wpe, exchange=args.exchange, gather_output=not args.no_gather_output)
+            if args.dump_outputs:
+                last[0] = r
 
     def sync():
         torch.cuda.synchronize()
@@ -564,6 +602,9 @@ def main():
         dt, n_launch, kern_ms, samples = measure_lookup(table, step, tok, ntok, args.steps, args.warmup, sync)
     else:
         dt, n_launch, kern_ms, samples = lookup_loop(cache, batches, wte, wpe, out, args.steps, args.warmup, sync, prefetch)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], d)
+    if emu is None and not sharded and not args.no_cpu_baseline:
         cache.embed_tokens(tok, wte=wte, wpe=wpe, out=out)       # `out` is compared with the oracle on the FIRST batch further down
         torch.cuda.synchronize()
     if dist is not None:
@@ -642,10 +683,10 @@ def main():
                             "steps": cs, "distinct_batches": len(bs)}
                 res["roofline"]["match_us"] = res["roofline"]["step_minus_kernel_us"]
                 res["roofline"]["match_us_kind"] = "ms_per_step - avg_kernel_ms: k_match_ell + the gap between the two launches"
-                if n_batches > 1 and not args.quick:     # (--quick runs sit under the counter passes: every launch a fresh batch)
+                if n_batches > 1 and args.full and not args.quick:     # (--quick runs sit under the counter passes: every launch a fresh batch)
                     res["roofline"]["same_batch"] = contrast(batches[:1], prefetch)
-                cache.embed_tokens(tok, wte=wte, wpe=wpe, out=out)       # (`out` = the first batch again, for the oracle check)
-                torch.cuda.synchronize()
+                    cache.embed_tokens(tok, wte=wte, wpe=wpe, out=out)       # (`out` = the first batch again, for the oracle check)
+                    torch.cuda.synchronize()
             except Exception as e:
                 res["roofline"]["match_us"] = None
                 res["roofline"]["contrast_error"] = repr(e)

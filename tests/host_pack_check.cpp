@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE -- the host-side key packing / probe-sequence / scale-slot helpers of scone_amd/csrc/scone_common.h
 // (the functions the index build, the match kernels and the table kernels share between host and device) compiled for the
 // HOST ONLY under AddressSanitizer + UBSan and checked for the properties the index relies on.  CPU only; built and run by
-// tests/test_host_logic.py::test_host_side_packing_under_sanitizers (hipcc --cuda-host-only -fsanitize=address,undefined).
+// tests/test_sanitizers_cpu.py::test_host_side_packing_under_sanitizers (hipcc --cuda-host-only
+// -fsanitize=address,undefined -fno-gpu-sanitize).
 #include <cstdio>
 #include <cstdlib>
 #include <map>

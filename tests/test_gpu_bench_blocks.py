@@ -1,6 +1,12 @@
 """GPU: the blocks bench.py adds around the headline (round 6) -- the `latency` block (the reference's own benchmark grid on a
 table, scone/configs/benchmark_config.json:79-82) and config C1 (the reference's CPU-runnable case through the GPU path) --
-run on small inputs, so that a broken block is found here and not in the driver's one bench run."""
+run on small inputs, so that a broken block is found here and not in the driver's one bench run.  Also the plain run
+itself: the headline alone, and the outputs it dumps."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -74,3 +80,39 @@ def test_alloc_output_keeps_the_fastest_candidate_and_changes_no_result():
     assert rep1 == {"candidates": 1, "kernel_ms": [None], "kept": 0} and plain.shape == out.shape
     f32, _ = cache.alloc_output(tok[:2], candidates=2, trials=1)                 # no wte / wpe: fp32 out
     assert f32.dtype == torch.float32 and cache.table.status() == 0
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_last_steps_output(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: K timed steps and none of the blocks that take runs of their own.
+    `--dump-outputs`: two runs with the same arguments dump identical arrays, and the rows are what a lookup of the LAST
+    timed step's batch returns (the bench's inputs rebuilt here from the same seeds)."""
+    import bench
+    from scone_amd import EmbeddingCache
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SCONE_ONE_DEVICE", "SCONE_DIST_BACKEND")}
+    steps, warmup, rows, B, T, d = 4, 1, 200_000, 64, 512, 768
+    args = ["--steps", str(steps), "--warmup", str(warmup), "--rows", str(rows), "--batch", str(B)]
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args, "--dump-outputs", str(tmp_path / run)], env=env,
+                           cwd=root, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == steps and r["warmup"] == warmup and r["roofline"]["kernel_ms"]["n"] == steps
+        assert abs(r["value"] - B * T * steps / (r["ms_per_step"] * steps * 1e-3)) / r["value"] < 1e-6
+        assert not set(r) & {"cpu_baseline", "latency", "configs", "sharded", "incomplete"}, sorted(r)
+        assert not set(r["roofline"]) & {"same_batch", "hbm_variant", "mall_variant"}, sorted(r["roofline"])
+    got = {n: [np.load(tmp_path / run / f"{n}.npy") for run in ("a", "b")] for n in ("embeddings", "embeddings_token_index")}
+    for n, (x, y) in got.items():
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    emb, idx = got["embeddings"][0], got["embeddings_token_index"][0].astype(np.int64)
+    assert emb.shape == (min(B * T, bench.DUMP_BYTES // (4 * d)), d) and np.isfinite(emb).all()
+    vocab_obj, keys, lens = bench.make_vocabulary(rows, "zipf")
+    cache = EmbeddingCache.from_synthetic(vocab_obj, d, table_format="int8", seed=7, base_scale=0.02 / 127)
+    _, batches = bench.make_batches(vocab_obj, keys, lens, "uniform", B, T, 1234, steps + warmup)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    wte = (torch.randn(50257, d, generator=g, device="cuda") * 0.02).half()
+    wpe = (torch.randn(1024, d, generator=g, device="cuda") * 0.01).half()
+    want = cache.embed_tokens(batches[steps + warmup - 1], wte=wte, wpe=wpe).reshape(-1, d)[torch.from_numpy(idx).cuda()]
+    assert np.array_equal(emb, want.float().cpu().numpy())

@@ -304,7 +304,7 @@ def test_bench_two_ranks_launched_like_the_driver(mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "5", "--warmup", "2", "--rows", "200000", "--batch", "256", "--table-mode", mode.split("-")[0],
-           "--sharded-rows-per-rank", "300000", "--sharded-steps", "2", "--pinned-rows", "300000", "--cpu-seconds", "1"]
+           "--sharded-rows-per-rank", "300000", "--sharded-steps", "2", "--pinned-rows", "300000", "--cpu-seconds", "1", "--full"]
     if mode == "sharded-slices":
         cmd.append("--no-gather-output")
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -402,7 +402,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     env.update(SCONE_DIST_BACKEND="gloo", SCONE_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONFAULTHANDLER="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "200000",
            "--batch", "128", "--sharded-rows-per-rank", "200000", "--sharded-steps", "1", "--pinned-rows", "200000",
-           "--cpu-seconds", "1"]
+           "--cpu-seconds", "1", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -293,6 +293,39 @@ def test_bench_refuses_more_ranks_than_devices():
     assert p.returncode != 0 and "HIP device" in p.stderr and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_a_fixed_sample(tmp_path, monkeypatch):
+    """A plain run measures the headline only; `--full` switches every other block on (each still subject to its --no-*
+    switch), `--quick` wins over `--full`, and `--steps` below 1 is refused.  `--dump-outputs` writes float32 rows of a
+    fixed, seeded sample of the token positions -- the same sample in every run, within 64 MB for every dim the bench
+    runs -- and the sample's positions (float64)."""
+    import bench
+    optional = ("no_cpu_baseline", "no_hbm_variant", "no_sharded_record", "no_configs", "no_latency")
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, "") and all(getattr(a, k) for k in optional)
+    a = bench.parse(["--full"])
+    assert a.full and not any(getattr(a, k) for k in optional)
+    a = bench.parse(["--full", "--no-configs"])
+    assert a.no_configs and not a.no_latency and not a.no_cpu_baseline
+    assert all(getattr(bench.parse(["--full", "--quick"]), k) for k in optional)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    for d in (768, 1024, 1280):
+        assert (bench.DUMP_BYTES // (4 * d)) * (4 * d + 8) <= 64 * 10**6
+    out = torch.randn(4, 300, 64).half()
+    bench.dump_outputs(str(tmp_path / "whole"), out, 64)
+    rows, idx = np.load(tmp_path / "whole" / "embeddings.npy"), np.load(tmp_path / "whole" / "embeddings_token_index.npy")
+    assert rows.dtype == np.float32 and idx.dtype == np.float64 and rows.shape == (1200, 64)
+    assert np.array_equal(idx, np.arange(1200)) and np.array_equal(rows, out.reshape(-1, 64).float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 4 * 64)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), out, 64)
+    ra, ia = np.load(tmp_path / "a" / "embeddings.npy"), np.load(tmp_path / "a" / "embeddings_token_index.npy")
+    assert ra.shape == (100, 64) and np.all(np.diff(ia) > 0) and 0 <= ia[0] and ia[-1] < 1200
+    assert np.array_equal(ra, out.reshape(-1, 64)[torch.from_numpy(ia.astype(np.int64))].float().numpy())
+    assert np.array_equal(ra, np.load(tmp_path / "b" / "embeddings.npy"))
+    assert np.array_equal(ia, np.load(tmp_path / "b" / "embeddings_token_index.npy"))
+
+
 def test_kernel_source_hash_covers_the_timed_kernels_translation_units():
     """`roofline.traffic` (and with it `roofline.frac`) is quoted only for the code it was measured on: the hash covers the
     scone_gather*.hip translation units, every header they include -- transitively, the public header too -- and the

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout 900 python bench.py --steps 50 --warmup 5 "$@" > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --steps 50 --warmup 5 --full "$@" > $O/bench.json 2> $O/bench.err
 tail -c 400 $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 # kernel trace and counters in separate runs (never --pmc together with other trace domains)
