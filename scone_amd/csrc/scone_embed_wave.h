@@ -20,10 +20,13 @@
 // wave_occupancy<> keeps the register budget free of spills).
 //
 // Same arithmetic as k_embed (scone_gather_impl.h): sequential fp32 accumulation in
-// the reference's list order, correctly rounded sum / K, (wte + mean) + wpe, one rounding to OutT.
+// the reference's list order, sum / K as IEEE division gives it for EVERY fp32 sum and every list length K >= 2
+// (scone_mean_div.h: a three-instruction quotient, redone by the true division where it would differ), (wte + mean) + wpe,
+// one rounding to OutT.
 #pragma once
 
 #include "scone_gather_impl.h"
+#include "scone_mean_div.h"
 #include "scone_probe.h"
 
 namespace scone_gather {
@@ -87,6 +90,16 @@ __device__ __forceinline__ void i4_accumulate(uint32_t w, float sc, float *acc) 
     acc[2 * b] = fmaf(sc16, (float)qe, acc[2 * b]);
     acc[2 * b + 1] = fmaf(sc16, (float)qo, acc[2 * b + 1]);
   }
+}
+
+// sum / K of a lane's elements.  fp32 / fp16 tables can hold anything (a sum may overflow, be subnormal, inf or NaN): the
+// full IEEE quotient.  A sum of INT8 / INT4 rows is +0 or a multiple of 2^-24 far below overflow, where the short form IS
+// the IEEE quotient (scone_mean_div.h).
+template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const int n, const int k) {
+  if constexpr (FMT == SCONE_FMT_I8 || FMT == SCONE_FMT_I4)
+    scone_mean_div_in_range(acc, n, k);
+  else
+    scone_mean_div(acc, n, k);
 }
 
 // Lane <-> element map.  A row is cut into segments of 512 elements; inside a segment lane l owns
@@ -331,16 +344,8 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
   }
 #ifndef SCONE_PROBE_NO_MATH
   if (reduce == SCONE_REDUCE_MEAN && kfull > 1) {
-    // engine.py:250: sum / K.  Correctly rounded quotient without the full division sequence
-    // (Markstein): y = RN(1/K); q0 = RN(x*y); r = x - q0*K (exact in an fma); q = RN(q0 + r*y).
-    const float kf = (float)kfull;
-    const float y = 1.0f / kf;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const float q0 = acc[e] * y;
-      const float r = fmaf(-kf, q0, acc[e]);
-      acc[e] = fmaf(r, y, q0);
-    }
+    // engine.py:250: sum / K, the IEEE quotient for every sum (overflowed to inf, subnormal, NaN): scone_mean_div.h
+    mean_div<FMT>(acc, EPL, kfull);
   }
 #endif
   uint32_t ow[NWO];
@@ -710,9 +715,7 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
       sc8[k] = __half2float(__ushort_as_half((unsigned short)((lrs[k] & 1) ? (w >> 16) : (w & 0xFFFFu))));
     }
   }
-  float kf = (float)kfull, y = 1.0f;
   const bool do_mean = reduce == SCONE_REDUCE_MEAN && kfull > 1;
-  if (do_mean) y = 1.0f / kf;
   for (int u = (int)lane; u < nu; u += 64) {
     uint32_t raw[KK][RW];
     uint32_t scw[KK];
@@ -763,14 +766,7 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
 #pragma unroll
       for (int e = 0; e < U; ++e) po[e] = __float_as_uint(acc[e]);
     } else {
-      if (do_mean) {
-#pragma unroll
-        for (int e = 0; e < U; ++e) {  // correctly rounded x / K (Markstein, see embed_token)
-          const float q0 = acc[e] * y;
-          const float r = fmaf(-kf, q0, acc[e]);
-          acc[e] = fmaf(r, y, q0);
-        }
-      }
+      if (do_mean) mean_div<FMT>(acc, U, kfull);  // IEEE x / K (scone_mean_div.h)
       uint32_t *po = reinterpret_cast<uint32_t *>(out_row) + (size_t)u * OW;
 #pragma unroll
       for (int w = 0; w < OW; ++w) {
@@ -927,16 +923,7 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
       }
     }
   }
-  if (reduce == SCONE_REDUCE_MEAN && K > 1) {  // correctly rounded x / K (Markstein, see embed_token)
-    const float kf = (float)K;
-    const float y = 1.0f / kf;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const float q0 = acc[e] * y;
-      const float r = fmaf(-kf, q0, acc[e]);
-      acc[e] = fmaf(r, y, q0);
-    }
-  }
+  if (reduce == SCONE_REDUCE_MEAN && K > 1) mean_div<FMT>(acc, EPL, K);  // IEEE x / K for any list length (scone_mean_div.h)
   uint32_t ow[NWO];
 #pragma unroll
   for (int w = 0; w < NWO; ++w) {
@@ -1085,16 +1072,7 @@ __global__ __launch_bounds__(256) void k_finalize_wave(const float *__restrict__
     float acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = __uint_as_float(sw[e]);
-    if (reduce == SCONE_REDUCE_MEAN && kfull > 1) {
-      const float kf = (float)kfull;
-      const float y = 1.0f / kf;
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) {  // correctly rounded x / K (see embed_token)
-        const float q0 = acc[e] * y;
-        const float r = fmaf(-kf, q0, acc[e]);
-        acc[e] = fmaf(r, y, q0);
-      }
-    }
+    if (reduce == SCONE_REDUCE_MEAN && kfull > 1) scone_mean_div(acc, EPL, kfull);  // IEEE x / K; the sums are the caller's buffer: always the full form
     uint32_t ow[NWO];
 #pragma unroll
     for (int w = 0; w < NWO; ++w) {

@@ -4,7 +4,7 @@
 Run in the build container only (``/root/reference`` does not exist on the GPU
 box and never travels):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [output directory, default: this one]
 
 It imports the reference's hot-path modules unmodified (one import shim for the
 missing ``scone.utils.cloud`` module), drives them on seeded
@@ -19,6 +19,8 @@ Reference functions exercised (paths relative to /root/reference):
     (they are inline in a method that needs an HF model)   scone/inference/engine.py:247-266
   * SconeLanguageModel.forward (unbound, on a stub holding a locally built GPT-2)
                                               scone/models/language_model.py:181-289
+
+edge.npz (make_edge) feeds the same functions the edge values built by tests/edge_fixture.py.
 """
 
 import os
@@ -31,6 +33,7 @@ import torch
 
 REF = os.environ.get("SCONE_REFERENCE", "/root/reference")
 HERE = os.path.dirname(os.path.abspath(__file__))
+OUT = sys.argv[1] if len(sys.argv) > 1 else HERE     # where the fixtures are written (default: in place)
 
 
 def import_reference():
@@ -118,7 +121,7 @@ def make_match(NGramExtractor):
     cases.append(name)
     out["cases"] = np.asarray(cases)
     out["n_streams"] = np.int64(6)
-    np.savez_compressed(os.path.join(HERE, "match.npz"), **out)
+    np.savez_compressed(os.path.join(OUT, "match.npz"), **out)
     print("match.npz:", len(cases), "cases")
 
 
@@ -180,8 +183,8 @@ def make_lookup(NGramExtractor, EmbeddingCache):
             assert torch.equal(re.get_embeddings(idlist), g_mem)
             if ci == 4:
                 # keep one tiny saved cache + extractor as on-disk format fixtures (data files)
-                ex.save(os.path.join(HERE, "tiny_extractor"))
-                mem.save(os.path.join(HERE, "tiny_cache"))
+                ex.save(os.path.join(OUT, "tiny_extractor"))
+                mem.save(os.path.join(OUT, "tiny_cache"))
         off, ids = csr_from_reference(ex, toks.tolist())
         out[f"{name}_keys"], out[f"{name}_lens"] = keys, lens
         out[f"{name}_max_n"] = np.int64(max_n)
@@ -197,7 +200,7 @@ def make_lookup(NGramExtractor, EmbeddingCache):
         out[f"{name}_agg_f16"] = agg_half.numpy()
         cases.append(name)
     out["cases"] = np.asarray(cases)
-    np.savez_compressed(os.path.join(HERE, "lookup.npz"), **out)
+    np.savez_compressed(os.path.join(OUT, "lookup.npz"), **out)
     print("lookup.npz:", len(cases), "cases")
 
 
@@ -236,8 +239,90 @@ def make_combine(SconeLanguageModel):
         out[f"{name}_embeds"] = captured["x"].numpy()
         cases.append(name)
     out["cases"] = np.asarray(cases)
-    np.savez_compressed(os.path.join(HERE, "combine.npz"), **out)
+    np.savez_compressed(os.path.join(OUT, "combine.npz"), **out)
     print("combine.npz:", len(cases), "cases")
+
+
+def make_edge(NGramExtractor, EmbeddingCache, SconeLanguageModel):
+    """Edge values (tests/edge_fixture.py builds the inputs: subnormals, sums that overflow, inf / NaN, fp16 / bf16 rounding
+    boundaries): what the reference's own mean (engine.py:247-266), its .half() and its forward's wte + mean + wpe
+    (language_model.py:234-254) return on them."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import edge_fixture as E
+    from transformers import GPT2Config, GPT2LMHeadModel
+    out = {}
+    cases = []
+    for max_n in (3, 4):
+        name = f"n{max_n}"
+        keys, lens = E.vocabulary(max_n)
+        n = len(lens)
+        ex = NGramExtractor(max_n=max_n, min_freq=1, max_f_grams=n)
+        ex.f_grams = {tuple(int(x) for x in keys[i, :lens[i]]) for i in range(n)}        # what fit() leaves behind
+        ex.f_gram_to_id = {tuple(int(x) for x in keys[i, :lens[i]]): i for i in range(n)}
+        ex.id_to_f_gram = {i: g for g, i in ex.f_gram_to_id.items()}
+        table = E.table(n, E.DIM, seed=max_n)
+        wte, wpe = E.wte_wpe(3, 64, E.DIM, seed=max_n)
+        mem = EmbeddingCache(ex, E.DIM)
+        mem.cache_embeddings(list(range(n)), torch.from_numpy(table), verbose=False)
+        cfg = GPT2Config(vocab_size=3, n_positions=64, n_embd=E.DIM, n_layer=1, n_head=2)
+        base = GPT2LMHeadModel(cfg).eval()
+        with torch.no_grad():
+            base.transformer.wte.weight.copy_(torch.from_numpy(wte))
+            base.transformer.wpe.weight.copy_(torch.from_numpy(wpe))
+        stub = types.SimpleNamespace(use_f_gram_embeddings=True, f_gram_model=None,
+                                     f_gram_projection=torch.nn.Identity(), base_model=base)
+        captured = {}
+
+        def hook(module, args, kwargs):
+            captured["x"] = kwargs["inputs_embeds"].detach().clone()
+
+        h = base.transformer.register_forward_pre_hook(hook, with_kwargs=True)
+        out[f"{name}_keys"], out[f"{name}_lens"], out[f"{name}_table"] = keys, lens, table
+        out[f"{name}_wte"], out[f"{name}_wpe"] = wte, wpe
+        streams = E.streams(max_n)
+        for si, tok in enumerate(streams):
+            B, T = tok.shape
+            means, offs, idl = [], [], []
+            for b in range(B):
+                toks = tok[b]
+                # the engine's aggregate lines, re-executed verbatim (engine.py:234-266)
+                token_f_grams = ex.get_token_f_grams(toks.tolist())
+                token_embeddings = {}
+                for pos, f_grams in token_f_grams.items():
+                    if not f_grams:
+                        continue
+                    f_gram_ids = [ex.f_gram_to_id[f_gram] for f_gram in f_grams]
+                    embeddings = mem.get_embeddings(f_gram_ids, torch.device("cpu"))
+                    token_embeddings[pos] = embeddings.mean(dim=0)
+                f_gram_embeddings = torch.zeros((1, len(toks), E.DIM), device="cpu")
+                for pos, embedding in token_embeddings.items():
+                    f_gram_embeddings[0, pos] = embedding
+                means.append(f_gram_embeddings)
+                off, ids = csr_from_reference(ex, toks.tolist())
+                offs.append(off + sum(len(x) for x in idl))
+                idl.append(ids)
+            fg = torch.cat(means, dim=0)
+            out[f"{name}_s{si}_tok"] = tok
+            out[f"{name}_s{si}_off"] = np.concatenate([o[:-1] for o in offs] + [offs[-1][-1:]])   # one CSR over the B * T tokens
+            out[f"{name}_s{si}_ids"] = np.concatenate(idl)
+            out[f"{name}_s{si}_mean_f32"] = fg.numpy()
+            out[f"{name}_s{si}_mean_f16"] = fg.half().numpy()
+            with torch.no_grad():
+                SconeLanguageModel.forward(stub, input_ids=torch.from_numpy(tok), f_gram_embeddings=fg)
+            out[f"{name}_s{si}_embeds"] = captured["x"].numpy()
+            if si == 4:                                                           # explicit position ids, one stream
+                pos = np.random.default_rng(50 + max_n).integers(0, 64, size=tok.shape)
+                with torch.no_grad():
+                    SconeLanguageModel.forward(stub, input_ids=torch.from_numpy(tok), f_gram_embeddings=fg,
+                                               position_ids=torch.from_numpy(pos))
+                out[f"{name}_s{si}_pos"] = pos
+                out[f"{name}_s{si}_embeds_pos"] = captured["x"].numpy()
+        h.remove()
+        out[f"{name}_n_streams"] = np.int64(len(streams))
+        cases.append(name)
+    out["cases"] = np.asarray(cases)
+    np.savez_compressed(os.path.join(OUT, "edge.npz"), **out)
+    print("edge.npz:", len(cases), "cases,", os.path.getsize(os.path.join(OUT, "edge.npz")), "bytes")
 
 
 CALLER_WORDS = ("the of and to in a is that for it as was with be by on not he this are or his from at which "
@@ -302,7 +387,7 @@ def make_callers(NGramExtractor):
     out["xf_texts"] = np.asarray(corpus_texts)
     out["xf_keys"], out["xf_lens"] = keys_arrays(xf.f_gram_to_id, 3)
     out["xf_args"] = np.asarray([3, 3, 250], dtype=np.int64)
-    np.savez_compressed(os.path.join(HERE, "callers.npz"), **out)
+    np.savez_compressed(os.path.join(OUT, "callers.npz"), **out)
     print("callers.npz:", len(texts), "texts,", len(lens), "f-grams")
 
 
@@ -312,6 +397,7 @@ def main():
     make_lookup(NGramExtractor, EmbeddingCache)
     make_combine(SconeLanguageModel)
     make_callers(NGramExtractor)
+    make_edge(NGramExtractor, EmbeddingCache, SconeLanguageModel)
 
 
 if __name__ == "__main__":

@@ -290,3 +290,110 @@ def test_extract_f_grams_fixture_is_reproduced_by_the_oracle(golden_dir):
     assert grams == want
     ex = extract_f_grams(texts, tok, max_n=max_n, min_freq=min_freq, max_f_grams=max_f, verbose=False, use_gpu=False)
     assert [ex.id_to_f_gram[i] for i in range(len(want))] == want
+
+
+# ------------------------------------------------------------------ edge values (tests/golden/edge.npz, tests/edge_fixture.py)
+def _edge():
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import edge_fixture as E
+    return E
+
+
+def test_edge_fixture_inputs_are_what_the_numpy_builder_builds(golden_dir):
+    """The GPU tests build wider tables with tests/edge_fixture.py; the fixture's own inputs come from the same code."""
+    E = _edge()
+    z = _load(golden_dir, "edge.npz")
+    for max_n in (3, 4):
+        c = f"n{max_n}"
+        keys, lens = E.vocabulary(max_n)
+        assert np.array_equal(keys, z[f"{c}_keys"]) and np.array_equal(lens, z[f"{c}_lens"])
+        assert E.same_bits(E.table(len(lens), E.DIM, seed=max_n), z[f"{c}_table"])
+        wte, wpe = E.wte_wpe(3, 64, E.DIM, seed=max_n)
+        assert E.same_bits(wte, z[f"{c}_wte"]) and E.same_bits(wpe, z[f"{c}_wpe"])
+        counts = np.zeros(16, dtype=np.int64)
+        for si, tok in enumerate(E.streams(max_n)):
+            assert np.array_equal(tok, z[f"{c}_s{si}_tok"])
+            counts += np.bincount(np.diff(z[f"{c}_s{si}_off"]), minlength=16)
+        kmax = max_n * (max_n + 1) // 2
+        assert np.all(counts[:kmax + 1] > 0) and counts[kmax] >= 50 and counts[kmax + 1:].sum() == 0, counts   # every K occurs
+
+
+def test_edge_fixture_oracle_bit_exact(golden_dir):
+    """oracle/ref_port.py (embed_numpy, combine, paper_embed) and oracle/oracle.c against what the reference computed on the
+    edge values: equal NaN positions, every other element bit for bit -- the fp32 mean, its .half(), wte + mean + wpe."""
+    from oracle.c_oracle import COracle
+    E = _edge()
+    z = _load(golden_dir, "edge.npz")
+    for c in z["cases"]:
+        keys, lens, max_n = z[f"{c}_keys"], z[f"{c}_lens"], int(c[1:])
+        table, wte, wpe = z[f"{c}_table"], z[f"{c}_wte"], z[f"{c}_wpe"]
+        co = COracle(keys, lens, max_n)
+        f2id = R._key_dict(keys, lens)
+        for si in range(int(z[f"{c}_n_streams"])):
+            tok = z[f"{c}_s{si}_tok"]
+            B, T = tok.shape
+            off, ids = R.hits_to_csr(R.match_hits(keys, lens, tok, max_n))
+            assert np.array_equal(off, z[f"{c}_s{si}_off"]) and np.array_equal(ids, z[f"{c}_s{si}_ids"]), (c, si)
+            want = z[f"{c}_s{si}_mean_f32"]
+            mean = R.embed_numpy(table, off, ids, "mean").reshape(B, T, -1)
+            assert E.same_bits(mean, want), (c, si, E.first_difference(mean, want))
+            assert E.same_bits(torch.from_numpy(mean).half().numpy(), z[f"{c}_s{si}_mean_f16"]), (c, si)
+            cm, total = co.embed(table, tok, "mean", nthreads=2)
+            assert total == len(ids) and E.same_bits(cm, want), (c, si, E.first_difference(cm, want))
+            x = R.combine(torch.from_numpy(tok), torch.from_numpy(mean), torch.from_numpy(wte), torch.from_numpy(wpe)).numpy()
+            assert E.same_bits(x, z[f"{c}_s{si}_embeds"]), (c, si, E.first_difference(x, z[f"{c}_s{si}_embeds"]))
+            if f"{c}_s{si}_pos" in z.files:
+                x = R.combine(torch.from_numpy(tok), torch.from_numpy(mean), torch.from_numpy(wte), torch.from_numpy(wpe),
+                              position_ids=torch.from_numpy(z[f"{c}_s{si}_pos"])).numpy()
+                assert E.same_bits(x, z[f"{c}_s{si}_embeds_pos"]), (c, si)
+            # the paper's lookup takes ONE row (no mean): where the reference's list has exactly that one row the two agree,
+            # and a row goes through unchanged whatever it holds
+            pe = R.paper_embed(f2id, max_n, tok, table)
+            hit = np.asarray([R.paper_lookup(f2id, max_n, tok[b].tolist()) for b in range(B)])
+            assert E.same_bits(pe[hit >= 0], table[hit[hit >= 0]])
+            assert not pe[hit < 0].any()
+
+
+def _shortcut(acc, k):
+    """The three-instruction quotient the wave kernels used before scone_mean_div.h, in numpy (fp32 operands; the two fma are
+    exact in float64 for these magnitudes and rounded once)."""
+    kf = np.float32(k)
+    y = np.float32(1) / kf
+    q0 = (acc * y).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        r = (acc.astype(np.float64) - q0.astype(np.float64) * np.float64(kf)).astype(np.float32)
+        return (q0.astype(np.float64) + r.astype(np.float64) * np.float64(y)).astype(np.float32)
+
+
+def test_edge_fixture_can_tell_the_shortcut_from_the_division(golden_dir):
+    """The fixture proves its own power: the old shortcut differs from the reference's mean on >= 1 % of band (a) at the
+    full covers K = 6 and K = 10, and bands (c) / (d) hold +inf and -inf means at K >= 2 (which the shortcut turns into NaN)."""
+    E = _edge()
+    z = _load(golden_dir, "edge.npz")
+    a, cd = E.band("a"), np.concatenate([E.band("c"), E.band("d")])
+    for c, kfull in (("n3", 6), ("n4", 10)):
+        table = z[f"{c}_table"]
+        differ = total = 0
+        seen_pinf = seen_ninf = shortcut_nan = 0
+        for si in range(int(z[f"{c}_n_streams"])):
+            off, ids = z[f"{c}_s{si}_off"], z[f"{c}_s{si}_ids"]
+            want = z[f"{c}_s{si}_mean_f32"].reshape(-1, table.shape[1])
+            sums = R.embed_numpy(table, off, ids, "sum")
+            K = np.diff(off)
+            m = K == kfull
+            got = _shortcut(sums[m][:, a], kfull)
+            differ += int((got.view(np.uint32) != want[m][:, a].view(np.uint32)).sum())
+            total += got.size
+            m2 = K >= 2
+            w = want[m2][:, cd]
+            seen_pinf += int(np.isposinf(w).sum())
+            seen_ninf += int(np.isneginf(w).sum())
+            for k in np.unique(K[m2]):
+                mk = K == k
+                sc = _shortcut(sums[mk][:, cd], int(k))
+                shortcut_nan += int((np.isnan(sc) & np.isinf(want[mk][:, cd])).sum())
+        assert total >= 50 * len(a) and differ >= 0.01 * total, (c, differ, total)
+        assert seen_pinf >= 1 and seen_ninf >= 1 and shortcut_nan >= seen_pinf + seen_ninf, (c, seen_pinf, seen_ninf, shortcut_nan)
+        print(f"{c}: shortcut differs on {differ}/{total} = {100 * differ / total:.1f} % of band (a) at K = {kfull}; "
+              f"{seen_pinf} +inf and {seen_ninf} -inf means in bands (c)/(d)")
