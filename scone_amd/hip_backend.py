@@ -432,11 +432,19 @@ class SconeTable:
                                                       C.byref(n)), "scone_profile_samples")
         return out[:n.value]
 
-    def embed_partial(self, tok: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def embed_partial(self, tok: torch.Tensor,
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """fp32 sums over the rows this shard owns ``[B*T, d]`` and the full hit counts ``[B*T]`` (``scone_embed_partial``);
+        ``out=(sums, counts)`` writes into the caller's buffers."""
         tok = self._tok(tok)
         B, T = tok.shape
-        partial = torch.empty((B * T, self.dim), dtype=torch.float32, device=self.device)
-        counts = torch.empty(B * T, dtype=torch.int32, device=self.device)
+        if out is None:
+            partial = torch.empty((B * T, self.dim), dtype=torch.float32, device=self.device)
+            counts = torch.empty(B * T, dtype=torch.int32, device=self.device)
+        else:
+            partial, counts = out
+            assert partial.is_cuda and partial.is_contiguous() and partial.dtype == torch.float32 and partial.shape == (B * T, self.dim)
+            assert counts.is_cuda and counts.is_contiguous() and counts.dtype == torch.int32 and counts.shape == (B * T,)
         with torch.cuda.device(self.device):
             rc = L.lib().scone_embed_partial(self._h, _ptr(tok), B, T, _ptr(partial), _ptr(counts), _stream())
         self._check(rc, "scone_embed_partial")
