@@ -224,6 +224,24 @@ int scone_gather_reduce(scone_handle *h, const int32_t *d_offsets, const int32_t
 int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_wte,
                 int64_t vocab, const void *d_wpe, int64_t n_pos, const int32_t *d_pos,
                 int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream);
+/* Packed variable-length batch (new here; the reference pads: batch_tokenize matches over the padded ids, so a pad id that
+ * occurs in an f-gram changes the lists of the last max_n - 1 real tokens of every sequence -- f_gram_tokenizer.py calls
+ * get_token_f_grams one sequence at a time, and that per-sequence result is what this call stands for).
+ * d_tok[total_tokens] holds the sequences back to back; d_cu_seqlens[n_seqs + 1] (int32, on the device) is non-decreasing with
+ * cu[0] = 0 and cu[n_seqs] = total_tokens; sequence s is [cu[s], cu[s+1]), empty sequences (repeated values) are allowed.
+ * Token p of sequence s gets exactly what scone_embed gives it when sequence s is passed alone as B = 1, T = cu[s+1] - cu[s]:
+ * the same id list in the reference's order, the same sequential fp32 sum, IEEE mean and (wte + fg) + wpe, in both lookup
+ * modes and with the handle's row_begin / row_end ownership rule.  d_out: [total_tokens, d].  d_pos: int32 [total_tokens] or
+ * NULL (= p - cu[s]).  The one-launch rule of scone_embed applies with total_tokens in place of B*T; larger batches use the
+ * id-record and position workspaces of the call's stream (scone_reserve).  Stream-ordered, no hidden synchronisation:
+ * total_tokens comes from the host.  total_tokens == 0 or n_seqs == 0: a no-op.
+ * SCONE_EINVAL (scone_last_error names the reason): negative n_seqs / total_tokens, a null d_tok / d_cu_seqlens / d_out,
+ * total_tokens > 2^31 - 1, a bad reduce / out_dtype, d % 8 != 0, a pinned-host table created with stage_tokens > 0 (its
+ * staging pipeline chunks whole rectangular sequences; tables read in place from pinned host memory work).  The CONTENTS of d_cu_seqlens are the caller's contract and are not validated on the device;
+ * whatever they are, no token outside d_tok[0, total_tokens) is read and nothing outside the total_tokens output rows written. */
+int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
+                       int64_t total_tokens, const void *d_wte, int64_t vocab, const void *d_wpe, int64_t n_pos,
+                       const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream);
 /* Pinned-host tables with a prefetch pipeline (cfg.stage_tokens > 0): start fetching for the NEXT batch now.  The first chunks
  * of (d_tok, B, T) are matched, their missing cold rows placed in the HBM cache and copied host -> HBM on the handle's side
  * streams, ordered behind `stream` (the stream on which the tokens are produced) -- or, tokens_ready != 0, behind nothing: the

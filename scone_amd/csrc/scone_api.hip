@@ -70,9 +70,10 @@ static scone_ws *scone_ws_acquire_once(scone_handle *h, hipStream_t s) {
       if (victim) {  // locked by the try_lock above
         if (victim->d_hits) (void)hipFree(victim->d_hits);
         if (victim->d_ell) (void)hipFree(victim->d_ell);
+        if (victim->d_vpos) (void)hipFree(victim->d_vpos);
         if (victim->d_block_sums) (void)hipFree(victim->d_block_sums);
-        victim->d_hits = victim->d_ell = victim->d_block_sums = nullptr;
-        victim->hits_cap_tokens = victim->ell_cap_tokens = victim->block_sums_cap = 0;
+        victim->d_hits = victim->d_ell = victim->d_vpos = victim->d_block_sums = nullptr;
+        victim->hits_cap_tokens = victim->ell_cap_tokens = victim->vpos_cap_tokens = victim->block_sums_cap = 0;
         victim->stream = s;
         victim->last_use = h->ws_clock;
         return victim;  // still locked: the caller's
@@ -110,6 +111,17 @@ int scone_ensure_ell(scone_handle *h, scone_ws *w, int64_t ntok) {
   w->ell_cap_tokens = 0;
   SCONE_HIP(h, hipMalloc(&w->d_ell, (size_t)ntok * SCONE_ELL_W(h->cfg.max_n) * sizeof(int32_t)));
   w->ell_cap_tokens = ntok;
+  return SCONE_OK;
+}
+
+int scone_ensure_vpos(scone_handle *h, scone_ws *w, int64_t ntok) {
+  if (ntok < h->reserve_tokens) ntok = h->reserve_tokens;
+  if (ntok <= w->vpos_cap_tokens) return SCONE_OK;
+  if (w->d_vpos) SCONE_HIP(h, hipFree(w->d_vpos));
+  w->d_vpos = nullptr;
+  w->vpos_cap_tokens = 0;
+  SCONE_HIP(h, hipMalloc(&w->d_vpos, (size_t)ntok * sizeof(int32_t)));
+  w->vpos_cap_tokens = ntok;
   return SCONE_OK;
 }
 
@@ -264,6 +276,9 @@ extern "C" int scone_create(const scone_cfg *cfg, scone_handle **out) {
     h->match_tile = 0;
     ev = getenv("SCONE_MATCH_TILE");
     if (ev && *ev) h->match_tile = atoll(ev);
+    h->varlen_t = 0;  // 0: the packed stream is one row (measured best: scone_embed_varlen, scone_gather.hip)
+    ev = getenv("SCONE_VARLEN_T");
+    if (ev && *ev && atoll(ev) > 0 && atoll(ev) <= 0x7FFFFFFFll) h->varlen_t = atoll(ev);
   }
   CREATE_HIP(hipMalloc(&h->slots, cap * sizeof(scone_slot)));
   CREATE_HIP(hipMemset(h->slots, 0, cap * sizeof(scone_slot)));
@@ -376,6 +391,7 @@ extern "C" void scone_destroy(scone_handle *h) {
   for (scone_ws *w : h->ws) {
     if (w->d_hits) (void)hipFree(w->d_hits);
     if (w->d_ell) (void)hipFree(w->d_ell);
+    if (w->d_vpos) (void)hipFree(w->d_vpos);
     if (w->d_block_sums) (void)hipFree(w->d_block_sums);
     if (w->d_total) (void)hipFree(w->d_total);
     delete w;
@@ -429,6 +445,9 @@ extern "C" int scone_reserve(scone_handle *h, int64_t max_tokens) {
     w->mu.lock();
     scone_ws_lock lk(w);
     int rc = h->cfg.dim > 0 && h->cfg.dim % 8 == 0 ? scone_ensure_ell(h, w, max_tokens) : scone_ensure_hits(h, w, max_tokens);
+    if (rc) return rc;
+    // the packed lookup's position array lives beside the records; a workspace that has served one keeps it at the reserve
+    if (w->d_vpos) rc = scone_ensure_vpos(h, w, max_tokens);
     if (rc) return rc;
   }
   return SCONE_OK;

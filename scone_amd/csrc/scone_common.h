@@ -139,6 +139,8 @@ struct scone_ws {
   int64_t hits_cap_tokens = 0;
   int32_t *d_ell = nullptr;  // per-token id lists for the fused lookup, [tokens, SCONE_ELL_W(max_n)]
   int64_t ell_cap_tokens = 0;
+  int32_t *d_vpos = nullptr;  // per-token position inside its sequence, written by the packed (cu_seqlens) match, [tokens]
+  int64_t vpos_cap_tokens = 0;
   int32_t *d_block_sums = nullptr;
   int64_t block_sums_cap = 0;
   int64_t *d_total = nullptr;
@@ -159,6 +161,7 @@ struct scone_handle {
   std::mutex lookup_mu;  // held from the event on the caller's stream to the wait on it: one hop at a time per handle
   long long fused_max_tokens;  // batches up to this many tokens take the one-launch kernel (env SCONE_FUSED_MAX_TOKENS overrides)
   long long match_tile;        // > 0: positions per workgroup of k_match_ell fixed by env SCONE_MATCH_TILE (else whole residency rounds)
+  long long varlen_t;          // > 0: row length T' of the packed lookup's gather traversal [total / T', T'] + remainder, fixed by env SCONE_VARLEN_T
   // index
   scone_slot *slots;
   uint64_t cap;  // power of two
@@ -218,6 +221,7 @@ struct scone_ws_lock {
 };
 int scone_ensure_hits(scone_handle *h, scone_ws *w, int64_t ntok);
 int scone_ensure_ell(scone_handle *h, scone_ws *w, int64_t ntok);
+int scone_ensure_vpos(scone_handle *h, scone_ws *w, int64_t ntok);
 // CU reserve: where a large lookup is launched.  enter: *launch = s (no reserve), or the handle's masked stream, made to wait
 // for everything queued on s; leave: s waits for what was launched there.  enter takes lookup_mu when it hops, leave drops it.
 int scone_lookup_enter(scone_handle *h, hipStream_t s, hipStream_t *launch);
@@ -274,6 +278,9 @@ int scone_launch_match_ell(scone_handle *h, const int32_t *d_tok, int32_t B, int
 // explicit owned range; keep_pos: owned ids stay at their index in the full list (holes = -1)
 int scone_launch_match_ell_ex(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, int32_t *d_ell,
                               long long row_begin, long long row_end, int keep_pos, hipStream_t s);
+// packed batch: sequence s is [cu[s], cu[s+1]); d_vpos (or null) receives every token's position inside its sequence
+int scone_launch_match_ell_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu, int32_t n_seqs, long long total,
+                                  int32_t *d_ell, int32_t *d_vpos, hipStream_t s);
 #define SCONE_ELL_W(max_n) ((max_n) <= 3 ? 8 : 16)
 
 // table kernels on an arbitrary row store (scone_table.hip); used for the replicated head of a shard

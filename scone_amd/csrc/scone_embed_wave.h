@@ -510,19 +510,36 @@ __global__ __launch_bounds__(256, (wave_occupancy<FMT, OutT, D, MAXN, FIXED_POS,
 // One wave per token.  Lane c < NC probes candidate window c of the token (n = 1..MAXN, start ascending --
 // the reference's append order is the lane order); a wavefront ballot of the hits gives K and, bit by
 // bit, the compacted id list as scalars; from there on it is the same K-way body as k_embed_wave.
-template <int FMT, typename OutT, int D, int MAXN>
+// VARLEN (scone_embed_varlen): the batch is one packed stream, sequence s = [cu[s], cu[s+1]).  The wave finds its sequence with
+// an upper-bound search over cu[1 .. n_seqs] -- p is wave-uniform, so the search runs on scalar loads and scalar branches --
+// and uses i = p - cu[s] and the sequence's own length where the rectangular form uses p % T and T.  i is clamped to [0, p]
+// and the room behind p to total - p, so no token outside tok[0, total) is read whatever cu holds.
+template <int FMT, typename OutT, int D, int MAXN, bool VARLEN = false>
 __global__ __launch_bounds__(256) void k_embed_fused(const scone_row_store rows, const void *__restrict__ scales_v,
                                                      const scone_index_view ix, const int32_t *__restrict__ tok,
                                                      const int32_t *__restrict__ pos, const OutT *__restrict__ wte,
                                                      const OutT *__restrict__ wpe, const uint8_t *__restrict__ zero_row,
                                                      OutT *__restrict__ out, uint32_t *__restrict__ status,
-                                                     const wave_params q) {
+                                                     const wave_params q, const int32_t *__restrict__ cu, int n_seqs) {
   constexpr int NC = MAXN * (MAXN + 1) / 2;
   constexpr int NWO = wave_geom<FMT, D>::EPL * (int)sizeof(OutT) / 4;
   const uint32_t lane = threadIdx.x & 63;
   const long long p = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (p >= q.BT) return;
-  const int i = (int)(p % q.T);
+  int i, T;
+  if constexpr (VARLEN) {
+    int lo = 1, hi = n_seqs;  // smallest j in [1, n_seqs] with cu[j] > p
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (cu[mid] > (int)p) hi = mid; else lo = mid + 1;
+    }
+    long long ii = p - (long long)cu[lo - 1], rr = (long long)cu[lo] - p;
+    ii = ii < 0 ? 0 : (ii > p ? p : ii);
+    rr = rr < 0 ? 0 : (rr > q.BT - p ? q.BT - p : rr);
+    i = (int)ii, T = (int)(ii + rr);
+  } else {
+    i = (int)(p % q.T), T = q.T;
+  }
 
   // ---- match: lane c probes candidate c ------------------------------------------------------------
   int32_t my_id = -1;
@@ -531,7 +548,7 @@ __global__ __launch_bounds__(256) void k_embed_fused(const scone_row_store rows,
     cand_ns((int)lane, n, s);
     // the paper's lookup only asks for windows that END at this token (s = n - 1) and have n >= 2
     const bool wanted = q.mode == SCONE_MODE_COVER || (s == n - 1 && n >= 2);
-    if (wanted && n <= q.max_n && i - s >= 0 && i - s + n <= q.T) {
+    if (wanted && n <= q.max_n && i - s >= 0 && i - s + n <= T) {
       uint32_t k[SCONE_MAX_N] = {0u, 0u, 0u, 0u};
       bool ok = true;
 #pragma unroll
@@ -602,10 +619,17 @@ int try_launch_fused(scone_handle *h, const embed_args &a, hipStream_t s) {
   scone_index_view ix;
   scone_index_view_of(h, &ix);
   const unsigned blocks = (unsigned)((a.BT + 3) / 4);
-#define SCONE_FUSED(DD, NN)                                                                                       \
-  hipLaunchKernelGGL((k_embed_fused<FMT, OutT, DD, NN>), dim3(blocks), dim3(256), 0, s, a.tv.st,                  \
+#define SCONE_FUSED_V(DD, NN, VV)                                                                                 \
+  hipLaunchKernelGGL((k_embed_fused<FMT, OutT, DD, NN, VV>), dim3(blocks), dim3(256), 0, s, a.tv.st,              \
                      (const void *)a.tv.scales, ix, a.tok, a.pos, (const OutT *)a.wte, (const OutT *)a.wpe,       \
-                     (const uint8_t *)a.zero_row, (OutT *)a.out, a.status, q)
+                     (const uint8_t *)a.zero_row, (OutT *)a.out, a.status, q, a.cu, a.n_seqs)
+#define SCONE_FUSED(DD, NN)                 \
+  do {                                      \
+    if (a.cu)                               \
+      SCONE_FUSED_V(DD, NN, true);          \
+    else                                    \
+      SCONE_FUSED_V(DD, NN, false);         \
+  } while (0)
   if constexpr (wave_geom<FMT, 768>::OK) {
     if (a.tv.d == 768) {
       if (a.max_n <= 3) SCONE_FUSED(768, 3); else SCONE_FUSED(768, 4);
@@ -628,6 +652,7 @@ int try_launch_fused(scone_handle *h, const embed_args &a, hipStream_t s) {
     }
   }
 #undef SCONE_FUSED
+#undef SCONE_FUSED_V
   return -1;
 }
 

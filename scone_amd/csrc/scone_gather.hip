@@ -328,6 +328,94 @@ extern "C" int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int
   return scone_prof_end(h, s);
 }
 
+// Packed variable-length batch.  Two-kernel form: k_match_ell_varlen (scone_index.hip) knows the sequence boundaries and leaves
+// one id record and one position per token; from there on nothing depends on where a sequence begins, so the large-batch
+// kernels run unchanged with explicit positions and (B, T) as a mere TRAVERSAL of the packed stream.  Measured on the headline
+// table (tools/varlen_compare.py, profiles/r08b): the whole stream as ONE row (B = 1, T = total: a wave per token, 4
+// consecutive tokens per workgroup, no walk) 765 us per 1M tokens, rows of 128 / 512 / 2048 tokens walked by persistent
+// workgroups 792 / 778 / 780 us -- with per-token positions a walk has no position row to keep, and the hardware's own
+// workgroup dispatch balances better than the fixed runs.  So: one row.  SCONE_VARLEN_T=<T'> (scone_handle::varlen_t, A/B runs
+// and tests) takes [total / T', T'] plus one launch for the total % T' tokens left over; streams above 2^25 tokens take
+// T' = 512 (one workgroup per 4 tokens would not fit a grid).  Decode-size batches: k_embed_fused<VARLEN>, one launch.
+extern "C" int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
+                                  int64_t total_tokens, const void *d_wte, int64_t vocab, const void *d_wpe, int64_t n_pos,
+                                  const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream) {
+  int rc = need_table(h, "scone_embed_varlen: handle has no table (dim == 0)");
+  if (rc) return rc;
+  if (n_seqs < 0 || total_tokens < 0) return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: negative n_seqs or total_tokens");
+  if (total_tokens > 0x7FFFFFFFll) return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: total_tokens above 2^31 - 1");
+  if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: bad reduce");
+  if (out_dtype != SCONE_DT_F32 && out_dtype != SCONE_DT_F16 && out_dtype != SCONE_DT_BF16)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: bad out_dtype");
+  if (h->cfg.dim % 8 != 0)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: needs d % 8 == 0 (the lane-group fallback reads another record form)");
+  if (h->cfg.stage_tokens && h->rows_host)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: not for stage_tokens > 0 (the staging pipeline chunks whole rectangular sequences)");
+  if (total_tokens == 0 || n_seqs == 0) return SCONE_OK;
+  if (!d_tok || !d_cu_seqlens || !d_out) return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: null pointer");
+  if ((d_wte && vocab <= 0) || (d_wpe && n_pos <= 0))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: wte/wpe given without vocab/n_pos");
+  SCONE_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  const long long total = total_tokens;
+  embed_args a = {};
+  fill_table_view(h, a.tv);
+  a.BT = total, a.T = (int)total, a.max_n = h->cfg.max_n;
+  a.tok_begin = 0, a.ntok = total;
+  a.zero_row = h->d_zero_row, a.mode = (int)h->cfg.lookup_mode;
+  a.tok = d_tok, a.pos = d_pos, a.wte = d_wte, a.vocab = vocab, a.wpe = d_wpe, a.n_pos = n_pos;
+  a.reduce = reduce, a.out = d_out, a.status = h->d_status;
+  if (scone_embed_takes_one_launch(h, total)) {
+    a.fused = 1, a.cu = d_cu_seqlens, a.n_seqs = n_seqs;
+    rc = scone_prof_begin(h, s);
+    if (rc) return rc;
+    rc = launch_fmt(h, a, SRC_HITS, MODE_FULL, out_dtype, s);
+    if (rc) {
+      scone_prof_abort(h);
+      return rc;
+    }
+    return scone_prof_end(h, s);
+  }
+  // the workspace of THIS stream, held while the match that writes it and the lookups that read it are enqueued
+  scone_ws_lock ws(scone_ws_acquire(h, s));
+  if (!ws.w) return scone_fail(h, SCONE_ENOMEM, "scone_embed_varlen: out of memory");
+  rc = scone_ensure_ell(h, ws.w, total);
+  if (rc) return rc;
+  int32_t *vpos = nullptr;
+  if (d_wpe && !d_pos) {  // default positions p - cu[s]: written by the match
+    rc = scone_ensure_vpos(h, ws.w, total);
+    if (rc) return rc;
+    vpos = ws.w->d_vpos;
+    a.pos = vpos;
+  }
+  rc = scone_launch_match_ell_varlen(h, d_tok, d_cu_seqlens, n_seqs, total, ws.w->d_ell, vpos, s);
+  if (rc) return rc;
+  a.ell = ws.w->d_ell;
+  const long long row = h->varlen_t > 0 ? h->varlen_t : (total <= (1ll << 25) ? total : 512);
+  const long long Tp = total < row ? total : row;
+  const long long main_tok = total / Tp * Tp;
+  const size_t esz = out_dtype == SCONE_DT_F32 ? 4 : 2;
+  const int W = SCONE_ELL_W(h->cfg.max_n);
+  rc = scone_prof_begin(h, s);
+  if (rc) return rc;
+  a.BT = main_tok, a.ntok = main_tok, a.T = (int)Tp;
+  rc = launch_fmt(h, a, SRC_HITS, MODE_FULL, out_dtype, s);
+  if (!rc && main_tok < total) {
+    embed_args r = a;
+    r.BT = total - main_tok, r.ntok = r.BT, r.T = (int)r.BT;
+    r.tok = a.tok + main_tok, r.ell = a.ell + main_tok * W;
+    r.pos = a.pos ? a.pos + main_tok : nullptr;
+    r.out = reinterpret_cast<uint8_t *>(a.out) + (size_t)main_tok * h->cfg.dim * esz;
+    rc = launch_fmt(h, r, SRC_HITS, MODE_FULL, out_dtype, s);
+  }
+  if (rc) {
+    scone_prof_abort(h);
+    return rc;
+  }
+  return scone_prof_end(h, s);
+}
+
 // All-gather form.  The gathered records (one per distinct row, every shard's) join the handle's row map with
 // scone_shard_gather_add_records -- all at once, or chunk by chunk as the all-gathers of a pipelined exchange complete --
 // and scone_shard_gather_embed_range reduces a run of sequences of the planned batch out of

@@ -180,6 +180,8 @@ struct embed_args {
   int reduce;
   int mode;           // SCONE_MODE_* (honoured by the wave kernels)
   int fused;          // decode-size batch: match inside the lookup kernel (k_embed_fused)
+  const int32_t *cu;  // packed batch (scone_embed_varlen), fused form only: sequence s = [cu[s], cu[s+1]); null = rectangle
+  int n_seqs;
   void *out;          // OutT [ntok, d]       (MODE_FULL / MODE_FINALIZE)
   float *partial;     // fp32 [ntok, d]       (MODE_PARTIAL)
   int32_t *counts;    // [ntok] full K        (MODE_PARTIAL out / MODE_FINALIZE in)

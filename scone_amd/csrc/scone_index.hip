@@ -127,21 +127,22 @@ struct __attribute__((aligned(16))) probe_req {
 // Phase 1, one thread per window start: tokens -> keys; unigrams resolve through the direct table, every
 // other window is first tested against the presence bitmap (a clear bit proves a miss; the bitmap is
 // small enough to live in L2) and, if it survives, queued for phase 2.
+// `room`: tokens from `start` to the end of ITS sequence (the caller's boundary rule: T - start % T for a rectangle, cu[s+1] -
+// start for a packed batch; 0 = no window starts here): tokens start .. start + room - 1 are read, nothing else.
 template <int MAXN>
 __device__ __forceinline__ void stage_starts(const int32_t *__restrict__ uni, int uni_cap, const uint32_t *__restrict__ bloom,
-                                             unsigned long long bloom_mask, const int32_t *__restrict__ tok, long long BT,
-                                             int T, int max_n, long long start, int t, int32_t (*win)[ELL_TILE],
-                                             probe_req *queue, uint32_t *q_count) {
+                                             unsigned long long bloom_mask, const int32_t *__restrict__ tok, int max_n,
+                                             long long start, int room, int t, int32_t (*win)[ELL_TILE], probe_req *queue,
+                                             uint32_t *q_count) {
   int32_t res[MAXN];
 #pragma unroll
   for (int n = 0; n < MAXN; ++n) res[n] = -1;
-  if (start >= 0 && start < BT) {
-    const int i = BT <= 0x7FFFFFFFll ? (int)((unsigned)start % (unsigned)T) : (int)(start % T);
+  if (room > 0) {
     uint32_t k[SCONE_MAX_N] = {0u, 0u, 0u, 0u};
     int nvalid = 0;  // longest window starting here that fits in the sequence and has only valid tokens
 #pragma unroll
     for (int j = 0; j < MAXN; ++j) {
-      if (j < max_n && i + j < T && nvalid == j) {
+      if (j < max_n && j < room && nvalid == j) {
         const int32_t v = tok[start + j];
         if (v >= 0) {
           k[j] = (uint32_t)v;
@@ -217,36 +218,13 @@ __device__ __forceinline__ void resolve_queue(const scone_slot *__restrict__ slo
   }
 }
 
+// Phase 3: position p (thread t, at place i of its sequence) compacts the candidates covering it -- windows of length nn that
+// start s <= i positions back, never in front of the sequence's first token -- into its record.
 template <int MAXN>
-__global__ __launch_bounds__(ELL_TILE) void k_match_ell(const scone_slot *__restrict__ slots, unsigned long long mask,
-                                                        const int32_t *__restrict__ uni, int uni_cap,
-                                                        const uint32_t *__restrict__ bloom, unsigned long long bloom_mask,
-                                                        const int32_t *__restrict__ tok, long long BT, int T, int max_n,
-                                                        long long row_begin, long long row_end, int mode,
-                                                        int keep_pos, int32_t *__restrict__ ell, int tile) {
-  constexpr int HALO = MAXN - 1;
+__device__ __forceinline__ void compact_record(const int32_t (*win)[ELL_TILE], int t, int i, long long p, int max_n,
+                                               long long row_begin, long long row_end, int mode, int keep_pos,
+                                               int32_t *__restrict__ ell) {
   constexpr int W = MAXN <= 3 ? 8 : 16;
-  // `tile` <= ELL_TILE - HALO positions per workgroup (the launcher sizes it so that the grid is a whole number of
-  // residency rounds); threads past tile + HALO only keep the barriers company
-  __shared__ int32_t win[MAXN][ELL_TILE];
-  __shared__ probe_req queue[MAXN * ELL_TILE];  // worst case: every window survives the bitmap
-  __shared__ uint32_t q_count;
-  const int t = threadIdx.x;
-  // Thread t stages the windows that START at position p = tile0 - HALO + t and later compacts the
-  // candidates covering p; the first HALO threads only supply the starts in front of the tile (one pass
-  // per thread: a second, 2-lane pass for the halo would double wave 0's dependent-load chain and with
-  // it, through the barrier, the whole workgroup's).
-  const long long p = (long long)blockIdx.x * tile - HALO + t;
-
-  if (t == 0) q_count = 0;
-  __syncthreads();
-  stage_starts<MAXN>(uni, uni_cap, bloom, bloom_mask, tok, BT, T, max_n, t < tile + HALO ? p : -1ll, t, win, queue, &q_count);
-  __syncthreads();
-  resolve_queue(slots, mask, t, &win[0][0], queue, q_count);
-  __syncthreads();
-
-  if (t < HALO || t >= tile + HALO || p >= BT) return;
-  const int i = BT <= 0x7FFFFFFFll ? (int)((unsigned)p % (unsigned)T) : (int)(p % T);
   int32_t rec[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) rec[j] = -1;
@@ -291,6 +269,92 @@ __global__ __launch_bounds__(ELL_TILE) void k_match_ell(const scone_slot *__rest
   int4 *dst = reinterpret_cast<int4 *>(ell + p * W);
 #pragma unroll
   for (int j = 0; j < W / 4; ++j) dst[j] = make_int4(rec[4 * j], rec[4 * j + 1], rec[4 * j + 2], rec[4 * j + 3]);
+}
+
+template <int MAXN>
+__global__ __launch_bounds__(ELL_TILE) void k_match_ell(const scone_slot *__restrict__ slots, unsigned long long mask,
+                                                        const int32_t *__restrict__ uni, int uni_cap,
+                                                        const uint32_t *__restrict__ bloom, unsigned long long bloom_mask,
+                                                        const int32_t *__restrict__ tok, long long BT, int T, int max_n,
+                                                        long long row_begin, long long row_end, int mode,
+                                                        int keep_pos, int32_t *__restrict__ ell, int tile) {
+  constexpr int HALO = MAXN - 1;
+  // `tile` <= ELL_TILE - HALO positions per workgroup (the launcher sizes it so that the grid is a whole number of
+  // residency rounds); threads past tile + HALO only keep the barriers company
+  __shared__ int32_t win[MAXN][ELL_TILE];
+  __shared__ probe_req queue[MAXN * ELL_TILE];  // worst case: every window survives the bitmap
+  __shared__ uint32_t q_count;
+  const int t = threadIdx.x;
+  // Thread t stages the windows that START at position p = tile0 - HALO + t and later compacts the
+  // candidates covering p; the first HALO threads only supply the starts in front of the tile (one pass
+  // per thread: a second, 2-lane pass for the halo would double wave 0's dependent-load chain and with
+  // it, through the barrier, the whole workgroup's).
+  const long long p = (long long)blockIdx.x * tile - HALO + t;
+  // place in the sequence; a window must fit in T (n_gram_extractor.py:118)
+  int i = 0, room = 0;
+  if (t < tile + HALO && p >= 0 && p < BT) {
+    i = BT <= 0x7FFFFFFFll ? (int)((unsigned)p % (unsigned)T) : (int)(p % T);
+    room = T - i;
+  }
+
+  if (t == 0) q_count = 0;
+  __syncthreads();
+  stage_starts<MAXN>(uni, uni_cap, bloom, bloom_mask, tok, max_n, p, room, t, win, queue, &q_count);
+  __syncthreads();
+  resolve_queue(slots, mask, t, &win[0][0], queue, q_count);
+  __syncthreads();
+
+  if (t < HALO || t >= tile + HALO || p >= BT) return;
+  compact_record<MAXN>(win, t, i, p, max_n, row_begin, row_end, mode, keep_pos, ell);
+}
+
+// The packed form (scone_embed_varlen): the batch is ONE stream of `total` tokens, sequence s = [cu[s], cu[s+1]).  Same tile
+// scheme; what changes is where a thread gets (i, room) from: an upper-bound search of its position in cu[1 .. n_seqs] (the
+// smallest j with cu[j] > p; empty sequences -- repeated values -- are stepped over by construction), then i = p - cu[j-1],
+// room = cu[j] - p.  Every thread searches for ITS position, the halo threads included: a start in front of the tile that lies
+// in the previous sequence is limited by that sequence's own end, and the compaction never looks back past i = 0, so no window
+// crosses a boundary in either direction.  The array is a few KB (2048 sequences: 8 KB) and every thread of a workgroup walks
+// the same top of the search tree, so the ~log2(n_seqs) dependent loads are L1 / L2 hits.
+// cu's CONTENTS are the caller's contract; whatever they are, i is clamped to [0, p] and room to [0, total - p], so every token
+// read is inside tok[0, total) and every write inside the `total` records / positions.
+template <int MAXN>
+__global__ __launch_bounds__(ELL_TILE) void k_match_ell_varlen(const scone_slot *__restrict__ slots, unsigned long long mask,
+                                                               const int32_t *__restrict__ uni, int uni_cap,
+                                                               const uint32_t *__restrict__ bloom, unsigned long long bloom_mask,
+                                                               const int32_t *__restrict__ tok, const int32_t *__restrict__ cu,
+                                                               int n_seqs, int total, int max_n, long long row_begin,
+                                                               long long row_end, int mode, int32_t *__restrict__ ell,
+                                                               int32_t *__restrict__ pos_out, int tile) {
+  constexpr int HALO = MAXN - 1;
+  __shared__ int32_t win[MAXN][ELL_TILE];
+  __shared__ probe_req queue[MAXN * ELL_TILE];
+  __shared__ uint32_t q_count;
+  const int t = threadIdx.x;
+  const long long p = (long long)blockIdx.x * tile - HALO + t;
+  int i = 0, room = 0;
+  if (t < tile + HALO && p >= 0 && p < total) {
+    int lo = 1, hi = n_seqs;  // smallest j in [1, n_seqs] with cu[j] > p (n_seqs if the array breaks its contract)
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (cu[mid] > (int)p) hi = mid; else lo = mid + 1;
+    }
+    const long long begin = cu[lo - 1], end = cu[lo];
+    long long ii = p - begin, rr = end - p;
+    ii = ii < 0 ? 0 : (ii > p ? p : ii);
+    rr = rr < 0 ? 0 : (rr > total - p ? total - p : rr);
+    i = (int)ii, room = (int)rr;
+  }
+
+  if (t == 0) q_count = 0;
+  __syncthreads();
+  stage_starts<MAXN>(uni, uni_cap, bloom, bloom_mask, tok, max_n, p, room, t, win, queue, &q_count);
+  __syncthreads();
+  resolve_queue(slots, mask, t, &win[0][0], queue, q_count);
+  __syncthreads();
+
+  if (t < HALO || t >= tile + HALO || p >= total) return;
+  if (pos_out) pos_out[p] = i;
+  compact_record<MAXN>(win, t, i, p, max_n, row_begin, row_end, mode, 0, ell);
 }
 
 // ------------------------------------------------------------------ CSR
@@ -431,14 +495,11 @@ int scone_launch_match_ell(scone_handle *h, const int32_t *d_tok, int32_t B, int
   return scone_launch_match_ell_ex(h, d_tok, B, T, d_ell, (long long)h->cfg.row_begin, (long long)h->cfg.row_end, 0, s);
 }
 
-int scone_launch_match_ell_ex(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, int32_t *d_ell, long long rb,
-                              long long re, int keep_pos, hipStream_t s) {
-  const long long BT = (long long)B * T;
-  if (BT == 0) return SCONE_OK;
-  // Positions per workgroup: at most ELL_TILE - halo, and such that the grid is a whole number of residency rounds (a
-  // workgroup is 4 waves of 27 VGPRs and 15 KB of LDS: 8 fit a CU).  ceil(BT / 254) workgroups at 2048 x 512 tokens is
-  // 4129 = two rounds of 2048 and a third that is nearly empty (profiles/r02g/match_tail.md); smaller tiles, one more
-  // FULL round.  SCONE_MATCH_TILE=<n> fixes the tile (A/B experiments).
+// Positions per workgroup: at most ELL_TILE - halo, and such that the grid is a whole number of residency rounds (a
+// workgroup is 4 waves of 27 VGPRs and 15 KB of LDS: 8 fit a CU).  ceil(BT / 254) workgroups at 2048 x 512 tokens is
+// 4129 = two rounds of 2048 and a third that is nearly empty (profiles/r02g/match_tail.md); smaller tiles, one more
+// FULL round.  SCONE_MATCH_TILE=<n> fixes the tile (A/B experiments).
+static long long match_ell_tile(const scone_handle *h, long long BT) {
   const long long tile_max = ELL_TILE - (h->cfg.max_n <= 3 ? 2 : 3);
   const long long resident = (long long)h->n_cus * 8;
   long long blocks = (BT + tile_max - 1) / tile_max;
@@ -449,7 +510,15 @@ int scone_launch_match_ell_ex(scone_handle *h, const int32_t *d_tok, int32_t B, 
     if (tile > tile_max) tile = tile_max;
   }
   if (h->match_tile > 0 && h->match_tile <= tile_max) tile = h->match_tile;
-  blocks = (BT + tile - 1) / tile;
+  return tile;
+}
+
+int scone_launch_match_ell_ex(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, int32_t *d_ell, long long rb,
+                              long long re, int keep_pos, hipStream_t s) {
+  const long long BT = (long long)B * T;
+  if (BT == 0) return SCONE_OK;
+  const long long tile = match_ell_tile(h, BT);
+  const long long blocks = (BT + tile - 1) / tile;
   if (!scone_grid_fits((unsigned long long)blocks, ELL_TILE)) return scone_fail(h, SCONE_EINVAL, "scone_embed: too many tokens for one launch");
   if (h->cfg.max_n <= 3)
     hipLaunchKernelGGL((k_match_ell<3>), dim3((unsigned)blocks), dim3(ELL_TILE), 0, s, h->slots, h->cap - 1, h->d_uni,
@@ -457,6 +526,26 @@ int scone_launch_match_ell_ex(scone_handle *h, const int32_t *d_tok, int32_t B, 
   else
     hipLaunchKernelGGL((k_match_ell<4>), dim3((unsigned)blocks), dim3(ELL_TILE), 0, s, h->slots, h->cap - 1, h->d_uni,
                        SCONE_UNI_CAP, h->d_bloom, h->bloom_mask, d_tok, BT, T, h->cfg.max_n, rb, re, (int)h->cfg.lookup_mode, keep_pos, d_ell, (int)tile);
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}
+
+int scone_launch_match_ell_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu, int32_t n_seqs, long long total,
+                                  int32_t *d_ell, int32_t *d_vpos, hipStream_t s) {
+  if (total == 0 || n_seqs == 0) return SCONE_OK;
+  const long long tile = match_ell_tile(h, total);
+  const long long blocks = (total + tile - 1) / tile;
+  if (total > 0x7FFFFFFFll || !scone_grid_fits((unsigned long long)blocks, ELL_TILE))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: too many tokens for one launch");
+  const long long rb = (long long)h->cfg.row_begin, re = (long long)h->cfg.row_end;
+  if (h->cfg.max_n <= 3)
+    hipLaunchKernelGGL((k_match_ell_varlen<3>), dim3((unsigned)blocks), dim3(ELL_TILE), 0, s, h->slots, h->cap - 1, h->d_uni,
+                       SCONE_UNI_CAP, h->d_bloom, h->bloom_mask, d_tok, d_cu, (int)n_seqs, (int)total, h->cfg.max_n, rb, re,
+                       (int)h->cfg.lookup_mode, d_ell, d_vpos, (int)tile);
+  else
+    hipLaunchKernelGGL((k_match_ell_varlen<4>), dim3((unsigned)blocks), dim3(ELL_TILE), 0, s, h->slots, h->cap - 1, h->d_uni,
+                       SCONE_UNI_CAP, h->d_bloom, h->bloom_mask, d_tok, d_cu, (int)n_seqs, (int)total, h->cfg.max_n, rb, re,
+                       (int)h->cfg.lookup_mode, d_ell, d_vpos, (int)tile);
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
 }

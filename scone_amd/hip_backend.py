@@ -51,6 +51,38 @@ def _raise(code: int, msg: str):
     raise SconeError(text)
 
 
+class SconeInvalidArgument(SconeError, ValueError):
+    """``SCONE_EINVAL`` from a call whose refusals are part of its contract (``scone_embed_varlen``)."""
+
+
+def check_cu_seqlens(cu_seqlens, total: int) -> np.ndarray:
+    """Host-side validation of a packed batch's boundaries: ``cu_seqlens`` (list, numpy array or CPU tensor of ``n + 1``
+    integers) must start at 0, never decrease (repeats = empty sequences) and end at ``total``.  Returns it as a contiguous
+    int32 array; raises ``ValueError`` otherwise.  Runs without a GPU.  (A DEVICE tensor is never passed here: checking it would
+    need a synchronisation, so its contents are the caller's contract -- the kernels stay memory-safe whatever it holds.)"""
+    if isinstance(cu_seqlens, torch.Tensor):
+        if cu_seqlens.is_cuda:
+            raise TypeError("check_cu_seqlens validates host data; a device tensor is trusted as it is")
+        cu_seqlens = cu_seqlens.numpy()
+    cu = np.asarray(cu_seqlens)
+    if cu.ndim != 1 or cu.size < 1:
+        raise ValueError("cu_seqlens must be a 1-D array of n_seqs + 1 offsets")
+    if cu.dtype.kind not in "iu":
+        raise ValueError("cu_seqlens must hold integers")
+    cu = cu.astype(np.int64)
+    total = int(total)
+    if total > 2**31 - 1:
+        raise ValueError("a packed batch holds at most 2^31 - 1 tokens")
+    if cu[0] != 0:
+        raise ValueError(f"cu_seqlens must start at 0, not {int(cu[0])}")
+    if (np.diff(cu) < 0).any():
+        k = int(np.argmax(np.diff(cu) < 0))
+        raise ValueError(f"cu_seqlens must not decrease: cu[{k}] = {int(cu[k])} > cu[{k + 1}] = {int(cu[k + 1])}")
+    if cu[-1] != total:
+        raise ValueError(f"cu_seqlens must end at the number of tokens ({total}), not {int(cu[-1])}")
+    return np.ascontiguousarray(cu.astype(np.int32))
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -357,6 +389,55 @@ class SconeTable:
                             _REDUCE[reduce], out.data_ptr(), _DT[out_dtype], stream)
         if rc != L.OK:
             self._check(rc, "scone_embed")
+        return out
+
+    def embed_varlen(self, tok: torch.Tensor, cu_seqlens, wte: Optional[torch.Tensor] = None,
+                     wpe: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",
+                     out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_embed_varlen``: the fused lookup of a PACKED batch -> ``[total, d]``.  ``tok [total]`` holds the sequences back
+        to back, sequence ``s`` is ``tok[cu_seqlens[s]:cu_seqlens[s + 1]]``; every token gets what :meth:`embed` gives it when
+        its sequence is passed alone (no window crosses a boundary; the default position is the place inside the sequence).
+        ``cu_seqlens`` on the host (list / numpy / CPU tensor) is validated (:func:`check_cu_seqlens`, ``ValueError``); an
+        int32 device tensor is trusted -- no synchronisation either way."""
+        if tok.dim() != 1:
+            raise ValueError("embed_varlen takes the packed token ids as a 1-D tensor [total]")
+        if not (tok.dtype == torch.int32 and tok.is_cuda and tok.is_contiguous()):
+            tok = tok.to(device=self.device, dtype=torch.int32).contiguous()
+        total = tok.shape[0]
+        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+            if not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                    and cu_seqlens.numel() >= 1):
+                raise ValueError("a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+            cu = cu_seqlens
+        else:
+            cu = torch.from_numpy(check_cu_seqlens(cu_seqlens, total)).to(self.device)
+        n_seqs = cu.numel() - 1
+        if out_dtype is None:
+            out_dtype = wte.dtype if wte is not None else (wpe.dtype if wpe is not None else torch.float32)
+        for name, w in (("wte", wte), ("wpe", wpe)):
+            if w is not None:
+                if not (w.is_cuda and w.is_contiguous() and w.dtype == out_dtype and w.dim() == 2
+                        and w.shape[1] == self.dim):
+                    raise ValueError(f"{name} must be a contiguous [*, {self.dim}] {out_dtype} tensor on {self.device}")
+        if position_ids is not None:
+            position_ids = position_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            if position_ids.numel() != total:
+                raise ValueError(f"position_ids must hold one position per packed token ({total})")
+        if out is None:
+            out = torch.empty((total, self.dim), dtype=out_dtype, device=self.device)
+        else:
+            assert out.is_cuda and out.is_contiguous() and out.dtype == out_dtype and out.numel() == total * self.dim
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = L.lib().scone_embed_varlen(self._h, tok.data_ptr(), cu.data_ptr(), n_seqs, total,
+                                        None if wte is None else wte.data_ptr(), 0 if wte is None else wte.shape[0],
+                                        None if wpe is None else wpe.data_ptr(), 0 if wpe is None else wpe.shape[0],
+                                        None if position_ids is None else position_ids.data_ptr(), _REDUCE[reduce],
+                                        out.data_ptr(), _DT[out_dtype], stream)
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"scone_embed_varlen: {L.lib().scone_last_error(self._h).decode()} "
+                                       f"[{L.lib().scone_strerror(rc).decode()}]")
+        if rc != L.OK:
+            self._check(rc, "scone_embed_varlen")
         return out
 
     def embed_prefetch(self, tok: torch.Tensor, tokens_ready: bool = False) -> None:

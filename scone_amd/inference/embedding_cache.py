@@ -275,7 +275,7 @@ class EmbeddingCache:
     def embed_tokens(self, input_ids: torch.Tensor, *, reduce: str = "mean", wte: Optional[torch.Tensor] = None,
                      wpe: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                      out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
-                     check: bool = False, base: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     check: bool = False, base: Optional[torch.Tensor] = None, cu_seqlens=None) -> torch.Tensor:
         """Fused lookup for ``input_ids [B, T]`` -> ``[B, T, d]``:
 
             out[b, t] = (wte[input_ids[b, t]] + reduce_k row(f_gram_k)) + wpe[position_ids[b, t]]
@@ -289,7 +289,28 @@ class EmbeddingCache:
         ``base [B, T, d]`` instead of ``wte`` / ``wpe``: a dense tensor the caller has already computed (the
         ``inputs_embeds`` of language_model.py:239-243, say) -- ``out = base + reduce_k row(f_gram_k)``, one rounding to
         ``out_dtype`` (default: ``base``'s dtype); the match produces CSR lists and ``scone_gather_reduce`` consumes them.
+
+        ``cu_seqlens [n + 1]``: ``input_ids`` is a PACKED batch ``[total]`` (sequences back to back, sequence ``s`` =
+        ``input_ids[cu_seqlens[s]:cu_seqlens[s + 1]]``, see :meth:`pack_sequences`) -> ``[total, d]``; every token gets what
+        its sequence alone would give it, without padding (``scone_embed_varlen``; new here).  ``position_ids [total]``
+        defaults to the place inside the sequence.  Host ``cu_seqlens`` are validated (``ValueError``), a device tensor is
+        trusted.  Not together with ``base=``.
         """
+        if cu_seqlens is not None:
+            if base is not None:
+                raise ValueError("cu_seqlens= (a packed batch) cannot be combined with base=")
+            tok = torch.as_tensor(input_ids)
+            if tok.dim() != 1:
+                raise ValueError("with cu_seqlens=, input_ids must be the 1-D packed token ids [total]")
+            if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda):
+                from scone_amd.hip_backend import check_cu_seqlens
+                cu_seqlens = check_cu_seqlens(cu_seqlens, tok.shape[0])      # before any device work
+            table = self.to_device()
+            result = table.embed_varlen(tok, cu_seqlens, wte=wte, wpe=wpe, position_ids=position_ids, reduce=reduce,
+                                        out_dtype=out_dtype, out=out)
+            if check and table.status() & 1:
+                raise IndexError("index out of range in self")
+            return result
         if base is not None:
             if wte is not None or wpe is not None or position_ids is not None or out is not None:
                 raise ValueError("base= replaces wte / wpe / position_ids (and takes no out=)")
@@ -311,6 +332,19 @@ class EmbeddingCache:
         if check and table.status() & 1:
             raise IndexError("index out of range in self")
         return result
+
+    @staticmethod
+    def pack_sequences(seqs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Host helper for ragged batches: a list of token lists (or 1-D arrays / tensors; empty ones allowed) ->
+        ``(input_ids int32 [total], cu_seqlens int32 [n + 1])`` on the CPU, ready for ``embed_tokens(..., cu_seqlens=...)``."""
+        parts = [np.asarray(s.cpu() if isinstance(s, torch.Tensor) else s, dtype=np.int64).reshape(-1) for s in seqs]
+        cu = np.zeros(len(parts) + 1, dtype=np.int64)
+        if parts:
+            np.cumsum([len(x) for x in parts], out=cu[1:])
+        if cu[-1] > 2**31 - 1:
+            raise ValueError("a packed batch holds at most 2^31 - 1 tokens")
+        ids = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        return (torch.from_numpy(ids.clip(-1, 2**31 - 1).astype(np.int32)), torch.from_numpy(cu.astype(np.int32)))
 
     def prefetch_tokens(self, input_ids: torch.Tensor, tokens_ready: bool = False) -> None:
         """Tables in pinned host DRAM with ``stage_tokens > 0``: start fetching the cold rows of the NEXT batch now
