@@ -49,8 +49,12 @@ enum {
   SCONE_FMT_F32 = 0, /* [N,d] float                                     row_bytes 4d      */
   SCONE_FMT_F16 = 1, /* [N,d] IEEE half                                 row_bytes 2d      */
   SCONE_FMT_I8 = 2,  /* [N,d] int8 + scales[N] half (per row)           row_bytes d+2     */
-  SCONE_FMT_I4 = 3   /* [N,d/2] offset-binary nibbles (elem 2k = low)   row_bytes d/2+2*d/128
+  SCONE_FMT_I4 = 3,  /* [N,d/2] offset-binary nibbles (elem 2k = low)   row_bytes d/2+2*d/128
                         + scales[N,d/128] half (per 128-group)                            */
+  SCONE_FMT_BF16 = 4 /* [N,d] bfloat16 (the upper half of the fp32), no scales, d % 8 == 0   row_bytes 2d
+                        fp32 rows are stored with IEEE round-to-nearest-even (NaN stays a quiet NaN); a row reads
+                        back as bits << 16, so every lookup equals the fp32 lookup of the dequantised table
+                        bit for bit.  Appended: the values above and SCONE_ABI_VERSION are unchanged.   */
 };
 enum {
   SCONE_PLACE_HBM = 0,        /* rows in device memory                                              */

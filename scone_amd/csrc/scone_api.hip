@@ -157,6 +157,10 @@ static bool payload_geometry(const scone_cfg &c, size_t *payload, size_t *scale_
       if (d % 8) return false;
       *payload = 2 * d, *scale_bytes = 0;
       return true;
+    case SCONE_FMT_BF16:
+      if (d % 8) return false;
+      *payload = 2 * d, *scale_bytes = 0;
+      return true;
     case SCONE_FMT_I8:
       if (d % 16) return false;
       *payload = d, *scale_bytes = 2;
@@ -302,7 +306,7 @@ extern "C" int scone_create(const scone_cfg *cfg, scone_handle **out) {
   }
   if (cfg->dim > 0) {
     if (!payload_geometry(h->cfg, &h->row_payload_bytes, &h->scale_bytes_per_row)) {
-      h->err = "scone_create: dim not compatible with table_fmt (F32 %4, F16 %8, I8 %16, I4 %128)";
+      h->err = "scone_create: dim not compatible with table_fmt (F32 %4, F16 %8, I8 %16, I4 %128, BF16 %8)";
       rc = SCONE_EINVAL;
       goto fail;
     }

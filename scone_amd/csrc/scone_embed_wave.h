@@ -92,9 +92,31 @@ __device__ __forceinline__ void i4_accumulate(uint32_t w, float sc, float *acc) 
   }
 }
 
-// sum / K of a lane's elements.  fp32 / fp16 tables can hold anything (a sum may overflow, be subnormal, inf or NaN): the
-// full IEEE quotient.  A sum of INT8 / INT4 rows is +0 or a multiple of 2^-24 far below overflow, where the short form IS
-// the IEEE quotient (scone_mean_div.h).
+// bf16 rows (a bf16 is the upper half of its fp32: the value is bits << 16): acc[a], acc[a + 1] += the two elements of row
+// word w[k], k = 0 .. K - 1 in list order.  The shift and the mask have no operand but the loaded word, so left to itself the
+// scheduler unpacks every row as it arrives and the live registers of a token double (fp16 rows stay packed until their
+// convert + add: at d = 768, max_n = 3 that was 72 VGPRs with 44 B of scratch against the fp16 twin's 67 without).  The empty
+// asm statements emit nothing; they make the unpack of row k wait for the sum of rows 0 .. k - 1, and the first row of a
+// column for the column before it (`prev`), which is the order the compiler picks for fp16 by itself: one accumulator pair
+// in flight, the rows packed.  The arithmetic is the plain list-order sum.
+template <int K, int STRIDE>
+__device__ __forceinline__ void bf16_accumulate_column(const uint32_t *w, float &lo, float &hi, const float *prev) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    uint32_t ww = w[k * STRIDE];
+    if (k > 0)
+      asm("" : "+v"(ww) : "v"(lo), "v"(hi));
+    else if (prev)
+      asm("" : "+v"(ww) : "v"(prev[0]), "v"(prev[1]));
+    lo += __uint_as_float(ww << 16);
+    hi += __uint_as_float(ww & 0xFFFF0000u);
+  }
+}
+
+// sum / K of a lane's elements.  fp32 / fp16 / bf16 tables can hold anything (a sum may overflow, be subnormal, inf or NaN;
+// a bf16 row spans fp32's whole exponent range): the full IEEE quotient -- the `else` below is theirs, and a new format
+// belongs there unless its sums are provably in range.  A sum of INT8 / INT4 rows is +0 or a multiple of 2^-24 far below
+// overflow, where the short form IS the IEEE quotient (scone_mean_div.h).
 template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const int n, const int k) {
   if constexpr (FMT == SCONE_FMT_I8 || FMT == SCONE_FMT_I4)
     scone_mean_div_in_range(acc, n, k);
@@ -111,7 +133,8 @@ template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const in
 template <int FMT, int D> struct wave_geom {
   static constexpr int EPL = D / 64;  // elements per lane
   static constexpr int NSEG = (D + 511) / 512;
-  static constexpr int BPE4 = FMT == SCONE_FMT_F32 ? 16 : FMT == SCONE_FMT_F16 ? 8 : FMT == SCONE_FMT_I8 ? 4 : 2;  // bytes per 4 elements
+  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_BF16, "unknown table format");
+  static constexpr int BPE4 = FMT == SCONE_FMT_F32 ? 16 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 8 : FMT == SCONE_FMT_I8 ? 4 : 2;  // bytes per 4 elements (last arm: INT4)
   static constexpr int ROW_BYTES = D / 4 * BPE4;
   static constexpr int NBR = ROW_BYTES / 64;  // row bytes per lane
   static constexpr int seg_elems(int s) { return ((D - 512 * s) >= 512 ? 512 : (D - 512 * s)) / 64; }  // per lane
@@ -152,7 +175,7 @@ template <int FMT, int D> struct wave_geom {
 // Switches for A/B builds: SCONE_HIOCC_MASK (bit FMT), SCONE_HIOCC_SLACK_CUT (registers taken off the occupancy
 // estimate of the variant).
 #ifndef SCONE_HIOCC_MASK
-#define SCONE_HIOCC_MASK 15
+#define SCONE_HIOCC_MASK 31  // bit FMT: all five formats (bf16, bit 4, has fp16's geometry and gains what fp16 gains)
 #endif
 #ifndef SCONE_HIOCC_SLACK_CUT
 #define SCONE_HIOCC_SLACK_CUT 8
@@ -292,8 +315,23 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
   float acc[EPL];
 #pragma unroll
   for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+#ifndef SCONE_PROBE_NO_MATH
+  if constexpr (FMT == SCONE_FMT_BF16 && K > 0) {  // column by column (bf16_accumulate_column); every other format: the loop below
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
+    for (int s = 0; s < NSEG; ++s) {
+#pragma unroll
+      for (int i = 0; i < G::seg_row_words(s); ++i) {
+        const int a = G::seg_acc(s) + 2 * i;
+        bf16_accumulate_column<K, NWR>(&raw[0][G::seg_row_word0(s) + i], acc[a], acc[a + 1], a > 0 ? &acc[a - 2] : nullptr);
+      }
+    }
+  }
+  constexpr int KROWS = FMT == SCONE_FMT_BF16 ? 0 : K;
+#else
+  constexpr int KROWS = K;
+#endif
+#pragma unroll
+  for (int k = 0; k < KROWS; ++k) {
     float sc0 = 1.0f;
     if constexpr (FMT == SCONE_FMT_I8) {
       const long long lr = (long long)rec[k] - row_begin;
@@ -321,6 +359,8 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
         } else if constexpr (FMT == SCONE_FMT_F16) {
           acc[G::seg_acc(s) + 2 * i] += __half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu)));
           acc[G::seg_acc(s) + 2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w >> 16)));
+        } else if constexpr (FMT == SCONE_FMT_BF16) {
+          // (summed above, column by column: this loop has no iterations)
         } else if constexpr (FMT == SCONE_FMT_I8) {
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
@@ -328,6 +368,7 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
             acc[G::seg_acc(s) + 4 * i + b] = fmaf(sc, (float)q, acc[G::seg_acc(s) + 4 * i + b]);
           }
         } else {
+          static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
           i4_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
         }
       }
@@ -712,7 +753,7 @@ int launch_wave(scone_handle *h, const embed_args &a, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 // Any embedding dim that is a multiple of 8 (2048, 4096, ... -- the specialised kernel above covers
 // 768 / 1024 / 1280).  Same wave-per-token scheme and the same arithmetic; the row is walked in UNITS
-// of 8 elements (INT8 8 B, fp16 16 B, fp32 32 B, INT4 4 B per lane; 16 B of fp16 output), lane l
+// of 8 elements (INT8 8 B, fp16 / bf16 16 B, fp32 32 B, INT4 4 B per lane; 16 B of fp16 output), lane l
 // taking units l, l+64, ...: every access is a contiguous run, every 64-B sector is touched whole.
 // K stays a compile-time constant (switch outside the unit loop), so the K loads of a unit are issued
 // back to back.
@@ -722,7 +763,8 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
                                             int reduce, const uint8_t *__restrict__ wte_row,
                                             const uint8_t *__restrict__ wpe_row, uint8_t *__restrict__ out_row, uint32_t lane) {
   constexpr int U = 8;                                  // elements per unit
-  constexpr int RW = FMT == SCONE_FMT_F32 ? 8 : FMT == SCONE_FMT_F16 ? 4 : FMT == SCONE_FMT_I8 ? 2 : 1;  // row words per unit
+  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_BF16, "unknown table format");
+  constexpr int RW = FMT == SCONE_FMT_F32 ? 8 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 4 : FMT == SCONE_FMT_I8 ? 2 : 1;  // row words per unit (last arm: INT4)
   constexpr int OW = U * (int)sizeof(OutT) / 4;         // output words per unit
   constexpr int OPW = pack_io<OutT>::PER_WORD;
   constexpr int KK = K > 0 ? K : 1;
@@ -763,8 +805,13 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
     float acc[U];
 #pragma unroll
     for (int e = 0; e < U; ++e) acc[e] = 0.f;
+    if constexpr (FMT == SCONE_FMT_BF16 && K > 0) {  // column by column, as in embed_token
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
+      for (int i = 0; i < RW; ++i)
+        bf16_accumulate_column<K, RW>(&raw[0][i], acc[2 * i], acc[2 * i + 1], i > 0 ? &acc[2 * i - 2] : nullptr);
+    }
+#pragma unroll
+    for (int k = 0; k < (FMT == SCONE_FMT_BF16 ? 0 : K); ++k) {
       float sc = sc8[k];
       if constexpr (FMT == SCONE_FMT_I4) sc = __half2float(__ushort_as_half((unsigned short)scw[k]));
 #pragma unroll
@@ -775,6 +822,8 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
         } else if constexpr (FMT == SCONE_FMT_F16) {
           acc[2 * i] += __half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu)));
           acc[2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w >> 16)));
+        } else if constexpr (FMT == SCONE_FMT_BF16) {
+          // (summed above, column by column: this loop has no iterations)
         } else if constexpr (FMT == SCONE_FMT_I8) {
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
@@ -782,6 +831,7 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
             acc[4 * i + b] = fmaf(sc, (float)q, acc[4 * i + b]);
           }
         } else {
+          static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
           i4_accumulate(w, sc, acc);
         }
       }
@@ -936,6 +986,9 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
         } else if constexpr (FMT == SCONE_FMT_F16) {
           acc[G::seg_acc(s) + 2 * i] += __half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu)));
           acc[G::seg_acc(s) + 2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w >> 16)));
+        } else if constexpr (FMT == SCONE_FMT_BF16) {
+          acc[G::seg_acc(s) + 2 * i] += __uint_as_float(w << 16);  // a bf16 is the upper half of its fp32
+          acc[G::seg_acc(s) + 2 * i + 1] += __uint_as_float(w & 0xFFFF0000u);
         } else if constexpr (FMT == SCONE_FMT_I8) {
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
@@ -943,6 +996,7 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
             acc[G::seg_acc(s) + 4 * i + b] = fmaf(sc, (float)q, acc[G::seg_acc(s) + 4 * i + b]);
           }
         } else {
+          static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
           i4_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
         }
       }

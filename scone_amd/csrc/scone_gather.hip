@@ -32,6 +32,7 @@ int launch_fmt(scone_handle *h, const embed_args &a, int src, int mode, int out_
     case SCONE_FMT_F16: return launch_f16(h, a, src, mode, out_dtype, s);
     case SCONE_FMT_I8: return launch_i8(h, a, src, mode, out_dtype, s);
     case SCONE_FMT_I4: return launch_i4(h, a, src, mode, out_dtype, s);
+    case SCONE_FMT_BF16: return launch_bf16(h, a, src, mode, out_dtype, s);
     default: return scone_fail(h, SCONE_EINVAL, "unknown table_fmt");
   }
 }

@@ -28,6 +28,7 @@ template <> struct fmt_traits<SCONE_FMT_F32> { static constexpr int VEC = 4; };
 template <> struct fmt_traits<SCONE_FMT_F16> { static constexpr int VEC = 8; };
 template <> struct fmt_traits<SCONE_FMT_I8> { static constexpr int VEC = 16; };
 template <> struct fmt_traits<SCONE_FMT_I4> { static constexpr int VEC = 32; };
+template <> struct fmt_traits<SCONE_FMT_BF16> { static constexpr int VEC = 8; };
 
 struct table_view {
   scone_row_store st;    // payload rows (local): HBM part + pinned-host part
@@ -109,6 +110,12 @@ __device__ __forceinline__ void accumulate(float (&acc)[fmt_traits<FMT>::VEC], c
       acc[2 * i] += __half2float(__ushort_as_half((unsigned short)(w[i] & 0xFFFFu)));
       acc[2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w[i] >> 16)));
     }
+  } else if constexpr (FMT == SCONE_FMT_BF16) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // a bf16 is the upper half of its fp32: bits << 16
+      acc[2 * i] += __uint_as_float(w[i] << 16);
+      acc[2 * i + 1] += __uint_as_float(w[i] & 0xFFFF0000u);
+    }
   } else if constexpr (FMT == SCONE_FMT_I8) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -119,6 +126,7 @@ __device__ __forceinline__ void accumulate(float (&acc)[fmt_traits<FMT>::VEC], c
       }
     }
   } else {
+    static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -399,5 +407,6 @@ int launch_f32(scone_handle *h, const embed_args &a, int src, int mode, int out_
 int launch_f16(scone_handle *h, const embed_args &a, int src, int mode, int out_dtype, hipStream_t s);
 int launch_i8(scone_handle *h, const embed_args &a, int src, int mode, int out_dtype, hipStream_t s);
 int launch_i4(scone_handle *h, const embed_args &a, int src, int mode, int out_dtype, hipStream_t s);
+int launch_bf16(scone_handle *h, const embed_args &a, int src, int mode, int out_dtype, hipStream_t s);
 
 }  // namespace scone_gather

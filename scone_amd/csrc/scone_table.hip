@@ -6,7 +6,8 @@
 //   EmbeddingCache.get_embeddings                    scone/inference/embedding_cache.py:113-147
 //
 // Row formats are this library's own (the reference stores fp32 only); the numpy
-// statement of the quantisers is oracle/ref_port.py quantize_i8 / quantize_i4.
+// statement of the quantisers is oracle/ref_port.py quantize_i8 / quantize_i4; that of the bf16 rounding is
+// tests/bf16_fixture.py to_bf16_bits.
 #include "scone_common.h"
 
 #include <type_traits>
@@ -16,6 +17,16 @@ namespace {
 __device__ __forceinline__ float wave_max(float v) {
   for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
   return v;
+}
+
+// fp32 -> bfloat16 bits, IEEE round-to-nearest-even: a tie (low half 0x8000) goes to the even upper half, a finite value
+// beyond the largest bf16 carries into the exponent and becomes +-inf, fp32 subnormals round into bf16 subnormals, -0.0 and
+// +-inf pass through.  NaN is taken out first: the increment would carry a NaN with a high payload into the sign bit
+// (0x7FFFFFFF -> 0x8000 = -0.0) and a truncation could leave the infinity's 0x7F80; it stays a NaN with the quiet bit set.
+__device__ __forceinline__ unsigned short f32_to_bf16_bits(float x) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x0040u);
+  return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
 // One wave per row.  src row index = blockIdx-derived r; destination local row =
@@ -42,6 +53,9 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
   } else if (FMT == SCONE_FMT_F16) {
     __half *o = reinterpret_cast<__half *>(st.row(lr));
     for (int e = lane; e < d; e += 64) o[e] = __float2half_rn(x[e]);
+  } else if (FMT == SCONE_FMT_BF16) {
+    unsigned short *o = reinterpret_cast<unsigned short *>(st.row(lr));
+    for (int e = lane; e < d; e += 64) o[e] = f32_to_bf16_bits(x[e]);
   } else if (FMT == SCONE_FMT_I8) {
     float m = 0.f;
     for (int e = lane; e < d; e += 64) m = fmaxf(m, fabsf(x[e]));
@@ -124,9 +138,12 @@ __global__ __launch_bounds__(256) void k_fill_synth(unsigned long long row_begin
       for (int k = 0; k < 4; ++k) v[k] = rounded_f32((float)(int8_t)(word >> (8 * k)) * sf);
       if (FMT == SCONE_FMT_F32) {
         reinterpret_cast<float4 *>(st.row(lr))[w] = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
+      } else if (FMT == SCONE_FMT_F16) {
         __half *o = reinterpret_cast<__half *>(st.row(lr)) + 4 * w;
         for (int k = 0; k < 4; ++k) o[k] = __float2half_rn(v[k]);
+      } else if (FMT == SCONE_FMT_BF16) {
+        unsigned short *o = reinterpret_cast<unsigned short *>(st.row(lr)) + 4 * w;
+        for (int k = 0; k < 4; ++k) o[k] = f32_to_bf16_bits(v[k]);  // the same fp32 value the fp32 / fp16 tables round
       }
     }
   }
@@ -157,6 +174,9 @@ __global__ __launch_bounds__(256) void k_gather_rows(scone_row_store st, const _
   } else if (FMT == SCONE_FMT_F16) {
     const __half *x = reinterpret_cast<const __half *>(st.row(lr));
     for (int e = lane; e < d; e += 64) o[e] = __half2float(x[e]);
+  } else if (FMT == SCONE_FMT_BF16) {
+    const unsigned short *x = reinterpret_cast<const unsigned short *>(st.row(lr));
+    for (int e = lane; e < d; e += 64) o[e] = __uint_as_float((uint32_t)x[e] << 16);
   } else if (FMT == SCONE_FMT_I8) {
     const int8_t *x = reinterpret_cast<const int8_t *>(st.row(lr));
     const float sf = __half2float(scales[lr]);
@@ -181,6 +201,7 @@ int dispatch_fmt(int fmt, F &&f) {
     case SCONE_FMT_F16: f(std::integral_constant<int, SCONE_FMT_F16>()); return 0;
     case SCONE_FMT_I8: f(std::integral_constant<int, SCONE_FMT_I8>()); return 0;
     case SCONE_FMT_I4: f(std::integral_constant<int, SCONE_FMT_I4>()); return 0;
+    case SCONE_FMT_BF16: f(std::integral_constant<int, SCONE_FMT_BF16>()); return 0;
     default: return -1;
   }
 }

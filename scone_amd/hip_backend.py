@@ -12,7 +12,8 @@ from . import _lib as L
 
 _FMT = {"fp32": L.FMT_F32, "float32": L.FMT_F32, "f32": L.FMT_F32,
         "fp16": L.FMT_F16, "float16": L.FMT_F16, "f16": L.FMT_F16,
-        "int8": L.FMT_I8, "i8": L.FMT_I8, "int4": L.FMT_I4, "i4": L.FMT_I4}
+        "int8": L.FMT_I8, "i8": L.FMT_I8, "int4": L.FMT_I4, "i4": L.FMT_I4,
+        "bf16": L.FMT_BF16, "bfloat16": L.FMT_BF16}
 _PLACE = {"hbm": L.PLACE_HBM, "pinned_host": L.PLACE_PINNED_HOST}
 _REDUCE = {"mean": L.REDUCE_MEAN, "sum": L.REDUCE_SUM}
 _MODE = {"cover": L.MODE_COVER, "longest_suffix": L.MODE_LONGEST_SUFFIX}
@@ -27,13 +28,13 @@ def format_code(fmt) -> int:
     try:
         return _FMT[str(fmt).lower()]
     except KeyError:
-        raise ValueError(f"unknown table format {fmt!r} (fp32, fp16, int8, int4)") from None
+        raise ValueError(f"unknown table format {fmt!r} (fp32, fp16, int8, int4, bf16)") from None
 
 
 def row_bytes(fmt: int, d: int) -> int:
     """Algorithmic bytes per table row."""
     return {L.FMT_F32: 4 * d, L.FMT_F16: 2 * d, L.FMT_I8: d + 2,
-            L.FMT_I4: d // 2 + 2 * (d // I4_GROUP)}[fmt]
+            L.FMT_I4: d // 2 + 2 * (d // I4_GROUP), L.FMT_BF16: 2 * d}[fmt]
 
 
 class SconeError(RuntimeError):
@@ -262,10 +263,11 @@ class SconeTable:
         self._check(rc, "scone_table_upload")
 
     def payload_bytes(self) -> int:
-        return {L.FMT_F32: 4 * self.dim, L.FMT_F16: 2 * self.dim, L.FMT_I8: self.dim, L.FMT_I4: self.dim // 2}[self.fmt]
+        return {L.FMT_F32: 4 * self.dim, L.FMT_F16: 2 * self.dim, L.FMT_I8: self.dim, L.FMT_I4: self.dim // 2,
+                L.FMT_BF16: 2 * self.dim}[self.fmt]
 
     def scales_per_row(self) -> int:
-        return {L.FMT_F32: 0, L.FMT_F16: 0, L.FMT_I8: 1, L.FMT_I4: self.dim // I4_GROUP}[self.fmt]
+        return {L.FMT_F32: 0, L.FMT_F16: 0, L.FMT_I8: 1, L.FMT_I4: self.dim // I4_GROUP, L.FMT_BF16: 0}[self.fmt]
 
     def download(self, row0: int, nrows: int, rows: Optional[np.ndarray] = None,
                  scales: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:

@@ -5,7 +5,7 @@ constructor, attributes and method signatures (``cache_embeddings``,
 ``get_embeddings``, ``get_token_embeddings``, ``save``, ``load``), the same
 exceptions and the same on-disk formats.  Host attributes (``embeddings`` dict /
 ``memory_mapped_embeddings``) are kept as the reference keeps them; every *lookup*
-is served from a device copy of the table (fp32 / fp16 / INT8 / INT4 rows in HBM
+is served from a device copy of the table (fp32 / fp16 / bf16 / INT8 / INT4 rows in HBM
 or in pinned host memory) by the kernels behind ``include/scone_hip.h``.  There is
 no CPU fallback for lookups.
 
@@ -27,7 +27,8 @@ class EmbeddingCache:
     """Cache for f-gram embeddings (reference: embedding_cache.py:13-54).
 
     Extra keyword-only arguments select the device representation:
-        table_format: "fp32" (reference-exact), "fp16", "int8", "int4".
+        table_format: "fp32" (reference-exact), "fp16", "int8", "int4", "bf16" (the exact two-byte home of a table
+                      whose embeddings were produced in bfloat16; lookups equal the fp32 ones of those rows bit for bit).
         placement:    "hbm" or "pinned_host" (rows >= hot_rows stay in host DRAM, read over PCIe).
         hot_rows:     with "pinned_host", the head of the table (ids are frequency-ordered) kept in HBM.
         stage_tokens: with "pinned_host": 0 = rows are read in place over PCIe by the lookup kernel; > 0 =
