@@ -246,6 +246,31 @@ int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, con
 int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
                        int64_t total_tokens, const void *d_wte, int64_t vocab, const void *d_wpe, int64_t n_pos,
                        const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream);
+/* Fused lookup onto a DENSE base (new here: the caller already holds its token embeddings -- the inputs_embeds of
+ * language_model.py:239-243, a tensor-parallel or scaled wte, an adapter's output; replaces match_csr + gather_reduce(base),
+ * five launches and a host synchronise, by the one or two launches of scone_embed):
+ *   out[p,:] = cast( (base[p,:] + reduce_k row_k) + wpe[pos[p]] )
+ * scone_embed / scone_embed_varlen with the per-position row d_base[p,:] where those use wte[tok[p]].  d_base: [B*T, d]
+ * ([total_tokens, d]) in out_dtype, required.  The id lists, the sequential fp32 sum, the IEEE mean, zero-fill for K = 0, d_wpe
+ * == NULL (term omitted), d_pos == NULL (default positions) and the row_begin / row_end ownership rule (owned rows only,
+ * divisor = full K) are scone_embed's; on a SCONE_MODE_LONGEST_SUFFIX handle a matched f-gram REPLACES the base row, as it
+ * replaces the wte row there.  Token ids serve the match only: there is no vocabulary bound, a negative token matches nothing,
+ * and SCONE_ST_BAD_TOKEN is raised only for a position id outside [0, n_pos).  Same launches, workspaces and stream ordering
+ * as scone_embed / scone_embed_varlen (no hidden synchronisation but the staged first-bind exception above); every road of
+ * scone_embed takes a dense base (one launch, two kernels, any d % 8 == 0, the lane-group fallback for other dims, staged and
+ * in-place pinned-host tables, the CU reserve).
+ * In place: d_out == d_base is allowed and defined (a wavefront reads the words of row p in the lanes that store them, and no
+ * other wavefront touches that row).  Any OTHER overlap of the two [n, d] ranges returns SCONE_EINVAL.
+ * SCONE_EINVAL (scone_last_error names the reason): a null d_tok / d_base / d_out (/ d_cu_seqlens), negative sizes, a bad
+ * reduce / out_dtype, d_wpe with n_pos <= 0, a partial overlap, and for the packed call what scone_embed_varlen refuses
+ * (d % 8 != 0, stage_tokens > 0, total_tokens > 2^31 - 1).  B*T == 0 / total_tokens == 0: a no-op. */
+int scone_embed_base(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_base,
+                     const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce,
+                     void *d_out, int32_t out_dtype, scone_stream_t stream);
+int scone_embed_base_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
+                            int64_t total_tokens, const void *d_base, const void *d_wpe, int64_t n_pos,
+                            const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype,
+                            scone_stream_t stream);
 /* Pinned-host tables with a prefetch pipeline (cfg.stage_tokens > 0): start fetching for the NEXT batch now.  The first chunks
  * of (d_tok, B, T) are matched, their missing cold rows placed in the HBM cache and copied host -> HBM on the handle's side
  * streams, ordered behind `stream` (the stream on which the tokens are produced) -- or, tokens_ready != 0, behind nothing: the

@@ -34,7 +34,10 @@ namespace scone_gather {
 struct wave_params {
   long long BT;
   long long row_begin, row_end;
-  long long vocab, n_pos;
+  long long vocab, n_pos;  // vocab < 0 (scone_embed_base): the `wte` pointer is a DENSE base [BT, d] -- its row is the position p,
+                           // tok serves the match only and there is no vocabulary to check.  (A wave-uniform switch on a value the
+                           // token loop keeps in scalar registers anyway: a flag of its own cost k_embed_wave one more live SGPR,
+                           // one VGPR and, at bf16 output, 12 B of scratch.)
   int T;
   int max_n;
   int reduce;
@@ -250,12 +253,15 @@ __device__ __forceinline__ void st_out_row(uint8_t *__restrict__ row, uint32_t l
 // One token with exactly K owned rows: straight-line code, every load unconditional and
 // issued before the first use (the K-way switch in the kernel keeps K a compile-time constant,
 // so the row registers are plain scalars and the waits are exact vmcnt counts).
+// wte_row and out_row carry no __restrict__: scone_embed_base allows out == base, where they are the SAME row -- each lane
+// loads its words of the row (ld_out_row) before it stores the same words (st_out_row, same lane map), and no other wave
+// touches the row.
 template <int FMT, typename OutT, int D, int K, bool FIXED_POS, bool PARTIAL, bool WPE_LDS = false>
 __device__ __forceinline__ void embed_token(const scone_row_store &rows, const void *__restrict__ scales_v,
                                             const int32_t *__restrict__ rec, long long row_begin, int kfull, int reduce,
-                                            const uint8_t *__restrict__ wte_row, const uint8_t *__restrict__ wpe_row,
+                                            const uint8_t *wte_row, const uint8_t *__restrict__ wpe_row,
                                             const uint32_t (&wpe_words)[wave_geom<FMT, D>::EPL * (int)sizeof(OutT) / 4],
-                                            uint8_t *__restrict__ out_row, uint32_t lane,
+                                            uint8_t *out_row, uint32_t lane,
                                             const uint32_t *__restrict__ wpe_lds = nullptr) {
   using G = wave_geom<FMT, D>;
   constexpr int EPL = G::EPL, NWR = G::NBR / 4, NSEG = G::NSEG;
@@ -427,8 +433,8 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
 template <int FMT, typename OutT, int D, int MAXN, bool FIXED_POS, bool PARTIAL = false, bool HIOCC = false>
 __global__ __launch_bounds__(256, (wave_occupancy<FMT, OutT, D, MAXN, FIXED_POS, HIOCC>::WAVES)) void k_embed_wave(
     const scone_row_store rows, const void *__restrict__ scales_v, const int32_t *__restrict__ ell,
-    const int32_t *__restrict__ tok, const int32_t *__restrict__ pos, const OutT *__restrict__ wte,
-    const OutT *__restrict__ wpe, const uint8_t *__restrict__ zero_row, OutT *__restrict__ out,
+    const int32_t *__restrict__ tok, const int32_t *__restrict__ pos, const OutT *wte,
+    const OutT *__restrict__ wpe, const uint8_t *__restrict__ zero_row, OutT *out,
     int32_t *__restrict__ counts, uint32_t *__restrict__ status, const wave_params q) {
   constexpr int NC = MAXN * (MAXN + 1) / 2;
   constexpr int W = MAXN <= 3 ? 8 : 16;
@@ -483,11 +489,13 @@ __global__ __launch_bounds__(256, (wave_occupancy<FMT, OutT, D, MAXN, FIXED_POS,
 
   int32_t rec[W];
   load_rec(p, rec);
-  int32_t tokv = wte ? tok[p] : 0;
+  // dense base (q.vocab < 0, wave-uniform): the base row of position p is row p of `wte` -- the walk p += T gives its address
+  // directly, so no token id is loaded or prefetched and there is no vocabulary to check
+  int32_t tokv = (wte && q.vocab >= 0) ? tok[p] : 0;
   int32_t posv = (!FIXED_POS && wpe) ? pos[p] : 0;
 
   while (true) {
-    const bool tok_ok = wte && tokv >= 0 && (long long)tokv < q.vocab;
+    const bool tok_ok = wte && (q.vocab < 0 || (tokv >= 0 && (long long)tokv < q.vocab));
     bool pos_ok = true;
     if constexpr (!FIXED_POS) pos_ok = wpe && posv >= 0 && (long long)posv < q.n_pos;
     if ((wte && !tok_ok) || (!FIXED_POS && wpe && !pos_ok)) {
@@ -501,7 +509,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<FMT, OutT, D, MAXN, FIXED_POS,
 #else
     const bool use_wte = tok_ok && !(q.mode == SCONE_MODE_LONGEST_SUFFIX && kfull > 0);
 #endif
-    const uint8_t *wte_row = use_wte ? reinterpret_cast<const uint8_t *>(wte + (long long)tokv * D) : zero_row;
+    const uint8_t *wte_row = use_wte ? reinterpret_cast<const uint8_t *>(wte + (q.vocab < 0 ? p : (long long)tokv) * D) : zero_row;
     const uint8_t *wpe_row = zero_row;
     if constexpr (!FIXED_POS) {
       if (pos_ok) wpe_row = reinterpret_cast<const uint8_t *>(wpe + (long long)posv * D);
@@ -518,7 +526,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<FMT, OutT, D, MAXN, FIXED_POS,
     int32_t tokn = 0, posn = 0;
     if (more) {
       load_rec(pn, recn);
-      tokn = wte ? tok[pn] : 0;
+      tokn = (wte && q.vocab >= 0) ? tok[pn] : 0;
       posn = (!FIXED_POS && wpe) ? pos[pn] : 0;
     }
 #ifdef SCONE_LOCKSTEP
@@ -558,9 +566,9 @@ __global__ __launch_bounds__(256, (wave_occupancy<FMT, OutT, D, MAXN, FIXED_POS,
 template <int FMT, typename OutT, int D, int MAXN, bool VARLEN = false>
 __global__ __launch_bounds__(256) void k_embed_fused(const scone_row_store rows, const void *__restrict__ scales_v,
                                                      const scone_index_view ix, const int32_t *__restrict__ tok,
-                                                     const int32_t *__restrict__ pos, const OutT *__restrict__ wte,
+                                                     const int32_t *__restrict__ pos, const OutT *wte,
                                                      const OutT *__restrict__ wpe, const uint8_t *__restrict__ zero_row,
-                                                     OutT *__restrict__ out, uint32_t *__restrict__ status,
+                                                     OutT *out, uint32_t *__restrict__ status,
                                                      const wave_params q, const int32_t *__restrict__ cu, int n_seqs) {
   constexpr int NC = MAXN * (MAXN + 1) / 2;
   constexpr int NWO = wave_geom<FMT, D>::EPL * (int)sizeof(OutT) / 4;
@@ -620,16 +628,17 @@ __global__ __launch_bounds__(256) void k_embed_fused(const scone_row_store rows,
   }
 
   // ---- gather + reduce + combine: as k_embed_wave ----------------------------------------------------
-  const int32_t tokv = wte ? tok[p] : 0;
+  // dense base (q.vocab < 0): row p of `wte`; tok[] was read for the match windows only
+  const int32_t tokv = (wte && q.vocab >= 0) ? tok[p] : 0;
   const int32_t posv = wpe ? (pos ? pos[p] : i) : 0;
-  const bool tok_ok = wte && tokv >= 0 && (long long)tokv < q.vocab;
+  const bool tok_ok = wte && (q.vocab < 0 || (tokv >= 0 && (long long)tokv < q.vocab));
   const bool pos_ok = wpe && posv >= 0 && (long long)posv < q.n_pos;
   if ((wte && !tok_ok) || (wpe && !pos_ok)) {
     if (lane == 0) atomicOr(status, SCONE_ST_BAD_TOKEN);
   }
   // paper mode: a matched f-gram REPLACES the token embedding (Algorithm 2), so wte is skipped
   const bool use_wte = tok_ok && !(q.mode == SCONE_MODE_LONGEST_SUFFIX && kfull > 0);
-  const uint8_t *wte_row = use_wte ? reinterpret_cast<const uint8_t *>(wte + (long long)tokv * D) : zero_row;
+  const uint8_t *wte_row = use_wte ? reinterpret_cast<const uint8_t *>(wte + (q.vocab < 0 ? p : (long long)tokv) * D) : zero_row;
   const uint8_t *wpe_row = pos_ok ? reinterpret_cast<const uint8_t *>(wpe + (long long)posv * D) : zero_row;
   uint8_t *out_row = reinterpret_cast<uint8_t *>(out + p * D);
   uint32_t wpe_words[NWO];
@@ -657,12 +666,15 @@ int try_launch_fused(scone_handle *h, const embed_args &a, hipStream_t s) {
   q.BT = a.BT, q.T = a.T, q.max_n = a.max_n;
   q.row_begin = a.tv.row_begin, q.row_end = a.tv.row_end;
   q.vocab = a.vocab, q.n_pos = a.n_pos, q.reduce = a.reduce, q.mode = a.mode;
+  const void *wte = a.wte;
+  if (q.vocab < 0) q.vocab = 0;            // (a caller's negative vocab keeps meaning "no token is in range")
+  if (a.base) wte = a.base, q.vocab = -1;  // scone_embed_base: the dense base travels in the kernels' wte parameter
   scone_index_view ix;
   scone_index_view_of(h, &ix);
   const unsigned blocks = (unsigned)((a.BT + 3) / 4);
 #define SCONE_FUSED_V(DD, NN, VV)                                                                                 \
   hipLaunchKernelGGL((k_embed_fused<FMT, OutT, DD, NN, VV>), dim3(blocks), dim3(256), 0, s, a.tv.st,              \
-                     (const void *)a.tv.scales, ix, a.tok, a.pos, (const OutT *)a.wte, (const OutT *)a.wpe,       \
+                     (const void *)a.tv.scales, ix, a.tok, a.pos, (const OutT *)wte, (const OutT *)a.wpe,         \
                      (const uint8_t *)a.zero_row, (OutT *)a.out, a.status, q, a.cu, a.n_seqs)
 #define SCONE_FUSED(DD, NN)                 \
   do {                                      \
@@ -708,6 +720,9 @@ int launch_wave(scone_handle *h, const embed_args &a, hipStream_t s) {
   q.BT = a.BT, q.T = a.T, q.max_n = a.max_n;
   q.row_begin = a.tv.row_begin, q.row_end = a.tv.row_end;
   q.vocab = a.vocab, q.n_pos = a.n_pos, q.reduce = a.reduce, q.mode = a.mode;
+  const void *wte = a.wte;
+  if (q.vocab < 0) q.vocab = 0;            // (a caller's negative vocab keeps meaning "no token is in range")
+  if (a.base) wte = a.base, q.vocab = -1;  // scone_embed_base: the dense base travels in the kernels' wte parameter
   q.B = (int)(a.BT / a.T);
   q.pos_groups = (a.T + 3) / 4;
   // Grid = a whole number of residency rounds: a workgroup is one wave per SIMD, so WAVES of them fit a
@@ -740,11 +755,11 @@ int launch_wave(scone_handle *h, const embed_args &a, hipStream_t s) {
   }
   if (a.pos)
     hipLaunchKernelGGL((k_embed_wave<FMT, OutT, D, MAXN, false, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, a.tv.st,
-                       (const void *)a.tv.scales, a.ell, a.tok, a.pos, (const OutT *)a.wte, (const OutT *)a.wpe,
+                       (const void *)a.tv.scales, a.ell, a.tok, a.pos, (const OutT *)wte, (const OutT *)a.wpe,
                        (const uint8_t *)a.zero_row, (OutT *)a.out, (int32_t *)nullptr, a.status, q);
   else
     hipLaunchKernelGGL((k_embed_wave<FMT, OutT, D, MAXN, true, false, HI>), dim3((unsigned)blocks), dim3(256), 0, s, a.tv.st,
-                       (const void *)a.tv.scales, a.ell, a.tok, a.pos, (const OutT *)a.wte, (const OutT *)a.wpe,
+                       (const void *)a.tv.scales, a.ell, a.tok, a.pos, (const OutT *)wte, (const OutT *)a.wpe,
                        (const uint8_t *)a.zero_row, (OutT *)a.out, (int32_t *)nullptr, a.status, q);
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
@@ -760,8 +775,8 @@ int launch_wave(scone_handle *h, const embed_args &a, hipStream_t s) {
 template <int FMT, typename OutT, int K, bool PARTIAL>
 __device__ __forceinline__ void embed_units(const scone_row_store &rows, const void *__restrict__ scales_v,
                                             const int32_t *__restrict__ rec, long long row_begin, int d, int kfull,
-                                            int reduce, const uint8_t *__restrict__ wte_row,
-                                            const uint8_t *__restrict__ wpe_row, uint8_t *__restrict__ out_row, uint32_t lane) {
+                                            int reduce, const uint8_t *wte_row,  // (no __restrict__: out == base, see embed_token)
+                                            const uint8_t *__restrict__ wpe_row, uint8_t *out_row, uint32_t lane) {
   constexpr int U = 8;                                  // elements per unit
   static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_BF16, "unknown table format");
   constexpr int RW = FMT == SCONE_FMT_F32 ? 8 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 4 : FMT == SCONE_FMT_I8 ? 2 : 1;  // row words per unit (last arm: INT4)
@@ -859,9 +874,9 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
 template <int FMT, typename OutT, int MAXN, bool PARTIAL>
 __global__ __launch_bounds__(256) void k_embed_wave_any(const scone_row_store rows, const void *__restrict__ scales_v,
                                                         const int32_t *__restrict__ ell, const int32_t *__restrict__ tok,
-                                                        const int32_t *__restrict__ pos, const OutT *__restrict__ wte,
+                                                        const int32_t *__restrict__ pos, const OutT *wte,
                                                         const OutT *__restrict__ wpe, const uint8_t *__restrict__ zero_row,
-                                                        OutT *__restrict__ out, int32_t *__restrict__ counts,
+                                                        OutT *out, int32_t *__restrict__ counts,
                                                         uint32_t *__restrict__ status, const wave_params q, int d) {
   constexpr int NC = MAXN * (MAXN + 1) / 2;
   constexpr int W = MAXN <= 3 ? 8 : 16;
@@ -884,15 +899,15 @@ __global__ __launch_bounds__(256) void k_embed_wave_any(const scone_row_store ro
     if constexpr (PARTIAL) {
       if (lane == 0) counts[p] = kfull;
     } else {
-      const int32_t tokv = wte ? tok[p] : 0;
+      const int32_t tokv = (wte && q.vocab >= 0) ? tok[p] : 0;  // dense base (q.vocab < 0): row p of `wte`, no token id needed
       const int32_t posv = wpe ? (pos ? pos[p] : i) : 0;
-      const bool tok_ok = wte && tokv >= 0 && (long long)tokv < q.vocab;
+      const bool tok_ok = wte && (q.vocab < 0 || (tokv >= 0 && (long long)tokv < q.vocab));
       const bool pos_ok = wpe && posv >= 0 && (long long)posv < q.n_pos;
       if ((wte && !tok_ok) || (wpe && !pos_ok)) {
         if (lane == 0) atomicOr(status, SCONE_ST_BAD_TOKEN);
       }
       if (tok_ok && !(q.mode == SCONE_MODE_LONGEST_SUFFIX && kfull > 0))
-        wte_row = reinterpret_cast<const uint8_t *>(wte + (long long)tokv * d);
+        wte_row = reinterpret_cast<const uint8_t *>(wte + (q.vocab < 0 ? p : (long long)tokv) * d);
       if (pos_ok) wpe_row = reinterpret_cast<const uint8_t *>(wpe + (long long)posv * d);
     }
     uint8_t *out_row = reinterpret_cast<uint8_t *>(out + p * d);
@@ -917,6 +932,9 @@ int launch_wave_any(scone_handle *h, const embed_args &a, hipStream_t s) {
   q.BT = a.BT, q.T = a.T, q.max_n = a.max_n;
   q.row_begin = a.tv.row_begin, q.row_end = a.tv.row_end;
   q.vocab = a.vocab, q.n_pos = a.n_pos, q.reduce = a.reduce, q.mode = a.mode;
+  const void *wte = a.wte;
+  if (q.vocab < 0) q.vocab = 0;            // (a caller's negative vocab keeps meaning "no token is in range")
+  if (a.base) wte = a.base, q.vocab = -1;  // scone_embed_base: the dense base travels in the kernels' wte parameter
   q.B = (int)(a.BT / a.T);
   q.pos_groups = (a.T + 3) / 4;
   long long chunks = SCONE_WAVE_BLOCKS / q.pos_groups;
@@ -936,7 +954,7 @@ int launch_wave_any(scone_handle *h, const embed_args &a, hipStream_t s) {
     }
   }
   hipLaunchKernelGGL((k_embed_wave_any<FMT, OutT, MAXN, false>), dim3((unsigned)blocks), dim3(256), 0, s, a.tv.st,
-                     (const void *)a.tv.scales, a.ell, a.tok, a.pos, (const OutT *)a.wte, (const OutT *)a.wpe,
+                     (const void *)a.tv.scales, a.ell, a.tok, a.pos, (const OutT *)wte, (const OutT *)a.wpe,
                      (const uint8_t *)a.zero_row, (OutT *)a.out, (int32_t *)nullptr, a.status, q, a.tv.d);
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;

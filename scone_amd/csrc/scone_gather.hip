@@ -159,6 +159,7 @@ static int embed_staged_chunks(scone_handle *h, const embed_args &full, int32_t 
     a.tok = full.tok + t0;
     a.pos = full.pos ? full.pos + t0 : nullptr;
     a.out = reinterpret_cast<uint8_t *>(full.out) + (size_t)t0 * h->cfg.dim * esz;
+    if (full.base) a.base = reinterpret_cast<const uint8_t *>(full.base) + (size_t)t0 * h->cfg.dim * esz;  // dense base: same rows as out
     a.ell = scone_stage_ell(h, buf);
     a.tv.st.cold = scone_stage_rows(h);  // the records now hold n_hot + cache slot: the cold half of the row store is the cache
     if (h->scale_bytes_per_row) a.tv.scales = reinterpret_cast<const __half *>(scone_stage_scales(h));
@@ -242,21 +243,18 @@ extern "C" int scone_gather_reduce(scone_handle *h, const int32_t *d_offsets, co
   return launch_fmt(h, a, SRC_CSR, MODE_FULL, out_dtype, (hipStream_t)stream);
 }
 
-extern "C" int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_wte,
-                           int64_t vocab, const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce,
-                           void *d_out, int32_t out_dtype, scone_stream_t stream) {
-  int rc = need_table(h, "scone_embed: handle has no table (dim == 0)");
-  if (rc) return rc;
-  if (B < 0 || T < 0) return scone_fail(h, SCONE_EINVAL, "scone_embed: negative B or T");
+static int embed_packed(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs, long long total,
+                        const void *d_wte, int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos,
+                        const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, hipStream_t s);
+
+// The rectangular lookup behind scone_embed (d_base == NULL: the base row of a token is wte[tok]) and scone_embed_base (a dense
+// d_base [B*T, d]: the base row of position p is d_base[p]; the kernels take it in their wte parameter, wave_params::vocab < 0).
+// Arguments are validated by the two entry points.
+static int embed_rect(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_wte, int64_t vocab,
+                      const void *d_base, const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce, void *d_out,
+                      int32_t out_dtype, hipStream_t s) {
   const long long BT = (long long)B * T;
-  if (BT == 0) return SCONE_OK;
-  if (!d_tok || !d_out) return scone_fail(h, SCONE_EINVAL, "scone_embed: null pointer");
-  if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM)
-    return scone_fail(h, SCONE_EINVAL, "scone_embed: bad reduce");
-  if ((d_wte && vocab <= 0) || (d_wpe && n_pos <= 0))
-    return scone_fail(h, SCONE_EINVAL, "scone_embed: wte/wpe given without vocab/n_pos");
-  SCONE_ON_DEVICE(h);
-  hipStream_t s = (hipStream_t)stream;
+  int rc;
   embed_args a = {};
   fill_table_view(h, a.tv);
   a.BT = BT, a.T = T, a.max_n = h->cfg.max_n;
@@ -264,7 +262,7 @@ extern "C" int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int
   a.zero_row = h->d_zero_row, a.mode = (int)h->cfg.lookup_mode;
   rc = check_mode(h, "scone_embed: lookup_mode longest_suffix needs d % 8 == 0");
   if (rc) return rc;
-  a.tok = d_tok, a.pos = d_pos, a.wte = d_wte, a.vocab = vocab, a.wpe = d_wpe, a.n_pos = n_pos;
+  a.tok = d_tok, a.pos = d_pos, a.wte = d_wte, a.vocab = vocab, a.wpe = d_wpe, a.n_pos = n_pos, a.base = d_base;
   a.reduce = reduce, a.out = d_out, a.status = h->d_status;
   if (h->cfg.stage_tokens && h->rows_host) {
     if (!scone_wave_kernel_covers(h->cfg.table_fmt, h->cfg.dim))
@@ -299,13 +297,11 @@ extern "C" int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int
     if (rc) return rc;
     a.hits = ws.w->d_hits;
   }
-  a.tok = d_tok, a.pos = d_pos, a.wte = d_wte, a.vocab = vocab, a.wpe = d_wpe, a.n_pos = n_pos;
-  a.reduce = reduce, a.out = d_out, a.status = h->d_status;
 #ifdef SCONE_PROBE_PERM
   if (const char *e = getenv("SCONE_PROBE_PERM_PTR")) {
     const int32_t *perm = reinterpret_cast<const int32_t *>(strtoull(e, nullptr, 0));
     const int W = h->cfg.max_n <= 3 ? 8 : 16;
-    if (perm && a.ell && !d_pos) {
+    if (perm && a.ell && !d_pos && !d_base) {
       if (g_probe_cap < BT) {
         if (g_probe_buf) (void)hipFree(g_probe_buf);
         SCONE_HIP(h, hipMalloc(&g_probe_buf, (size_t)BT * (W + 2) * sizeof(int32_t)));
@@ -327,6 +323,77 @@ extern "C" int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int
     return rc;
   }
   return scone_prof_end(h, s);
+}
+
+extern "C" int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_wte,
+                           int64_t vocab, const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce,
+                           void *d_out, int32_t out_dtype, scone_stream_t stream) {
+  int rc = need_table(h, "scone_embed: handle has no table (dim == 0)");
+  if (rc) return rc;
+  if (B < 0 || T < 0) return scone_fail(h, SCONE_EINVAL, "scone_embed: negative B or T");
+  if ((long long)B * T == 0) return SCONE_OK;
+  if (!d_tok || !d_out) return scone_fail(h, SCONE_EINVAL, "scone_embed: null pointer");
+  if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed: bad reduce");
+  if ((d_wte && vocab <= 0) || (d_wpe && n_pos <= 0))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed: wte/wpe given without vocab/n_pos");
+  SCONE_ON_DEVICE(h);
+  return embed_rect(h, d_tok, B, T, d_wte, vocab, nullptr, d_wpe, n_pos, d_pos, reduce, d_out, out_dtype, (hipStream_t)stream);
+}
+
+// out == base is the in-place call (a wave reads the words of row p in the lanes that store them); any other overlap of the
+// two [n, d] ranges would let one wave's store reach a row another wave has not read yet.
+static bool base_overlaps_out(const void *d_base, const void *d_out, unsigned long long bytes) {
+  const unsigned long long b = (unsigned long long)reinterpret_cast<uintptr_t>(d_base), o = (unsigned long long)reinterpret_cast<uintptr_t>(d_out);
+  return b != o && b < o + bytes && o < b + bytes;
+}
+
+// Dense base (new here): the caller already holds its token embeddings (the inputs_embeds of language_model.py:239-243).
+extern "C" int scone_embed_base(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_base,
+                                const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce, void *d_out,
+                                int32_t out_dtype, scone_stream_t stream) {
+  int rc = need_table(h, "scone_embed_base: handle has no table (dim == 0)");
+  if (rc) return rc;
+  if (B < 0 || T < 0) return scone_fail(h, SCONE_EINVAL, "scone_embed_base: negative B or T");
+  if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base: bad reduce");
+  if (out_dtype != SCONE_DT_F32 && out_dtype != SCONE_DT_F16 && out_dtype != SCONE_DT_BF16)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base: bad out_dtype");
+  const long long BT = (long long)B * T;
+  if (BT == 0) return SCONE_OK;
+  if (!d_tok || !d_base || !d_out) return scone_fail(h, SCONE_EINVAL, "scone_embed_base: null pointer (d_tok, d_base and d_out are required)");
+  if (d_wpe && n_pos <= 0) return scone_fail(h, SCONE_EINVAL, "scone_embed_base: wpe given without n_pos");
+  if (base_overlaps_out(d_base, d_out, (unsigned long long)BT * h->cfg.dim * (out_dtype == SCONE_DT_F32 ? 4 : 2)))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base: d_base overlaps d_out (only d_out == d_base, the in-place call, is defined)");
+  SCONE_ON_DEVICE(h);
+  return embed_rect(h, d_tok, B, T, nullptr, 0, d_base, d_wpe, n_pos, d_pos, reduce, d_out, out_dtype, (hipStream_t)stream);
+}
+
+extern "C" int scone_embed_base_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
+                                       int64_t total_tokens, const void *d_base, const void *d_wpe, int64_t n_pos,
+                                       const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype,
+                                       scone_stream_t stream) {
+  int rc = need_table(h, "scone_embed_base_varlen: handle has no table (dim == 0)");
+  if (rc) return rc;
+  if (n_seqs < 0 || total_tokens < 0) return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: negative n_seqs or total_tokens");
+  if (total_tokens > 0x7FFFFFFFll) return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: total_tokens above 2^31 - 1");
+  if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: bad reduce");
+  if (out_dtype != SCONE_DT_F32 && out_dtype != SCONE_DT_F16 && out_dtype != SCONE_DT_BF16)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: bad out_dtype");
+  if (h->cfg.dim % 8 != 0)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: needs d % 8 == 0 (the lane-group fallback reads another record form)");
+  if (h->cfg.stage_tokens && h->rows_host)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: not for stage_tokens > 0 (the staging pipeline chunks whole rectangular sequences)");
+  if (total_tokens == 0 || n_seqs == 0) return SCONE_OK;
+  if (!d_tok || !d_cu_seqlens || !d_base || !d_out)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: null pointer (d_tok, d_cu_seqlens, d_base and d_out are required)");
+  if (d_wpe && n_pos <= 0) return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: wpe given without n_pos");
+  if (base_overlaps_out(d_base, d_out, (unsigned long long)total_tokens * h->cfg.dim * (out_dtype == SCONE_DT_F32 ? 4 : 2)))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_base_varlen: d_base overlaps d_out (only d_out == d_base, the in-place call, is defined)");
+  SCONE_ON_DEVICE(h);
+  return embed_packed(h, d_tok, d_cu_seqlens, n_seqs, total_tokens, nullptr, 0, d_base, d_wpe, n_pos, d_pos, reduce, d_out,
+                      out_dtype, (hipStream_t)stream);
 }
 
 // Packed variable-length batch.  Two-kernel form: k_match_ell_varlen (scone_index.hip) knows the sequence boundaries and leaves
@@ -358,14 +425,21 @@ extern "C" int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const i
   if ((d_wte && vocab <= 0) || (d_wpe && n_pos <= 0))
     return scone_fail(h, SCONE_EINVAL, "scone_embed_varlen: wte/wpe given without vocab/n_pos");
   SCONE_ON_DEVICE(h);
-  hipStream_t s = (hipStream_t)stream;
-  const long long total = total_tokens;
+  return embed_packed(h, d_tok, d_cu_seqlens, n_seqs, total_tokens, d_wte, vocab, nullptr, d_wpe, n_pos, d_pos, reduce, d_out,
+                      out_dtype, (hipStream_t)stream);
+}
+
+// The packed lookup behind scone_embed_varlen and scone_embed_base_varlen (d_base: as in embed_rect).
+static int embed_packed(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs, long long total,
+                        const void *d_wte, int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos,
+                        const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, hipStream_t s) {
+  int rc;
   embed_args a = {};
   fill_table_view(h, a.tv);
   a.BT = total, a.T = (int)total, a.max_n = h->cfg.max_n;
   a.tok_begin = 0, a.ntok = total;
   a.zero_row = h->d_zero_row, a.mode = (int)h->cfg.lookup_mode;
-  a.tok = d_tok, a.pos = d_pos, a.wte = d_wte, a.vocab = vocab, a.wpe = d_wpe, a.n_pos = n_pos;
+  a.tok = d_tok, a.pos = d_pos, a.wte = d_wte, a.vocab = vocab, a.wpe = d_wpe, a.n_pos = n_pos, a.base = d_base;
   a.reduce = reduce, a.out = d_out, a.status = h->d_status;
   if (scone_embed_takes_one_launch(h, total)) {
     a.fused = 1, a.cu = d_cu_seqlens, a.n_seqs = n_seqs;
@@ -408,6 +482,7 @@ extern "C" int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const i
     r.tok = a.tok + main_tok, r.ell = a.ell + main_tok * W;
     r.pos = a.pos ? a.pos + main_tok : nullptr;
     r.out = reinterpret_cast<uint8_t *>(a.out) + (size_t)main_tok * h->cfg.dim * esz;
+    if (a.base) r.base = reinterpret_cast<const uint8_t *>(a.base) + (size_t)main_tok * h->cfg.dim * esz;  // dense base: same rows as out
     rc = launch_fmt(h, r, SRC_HITS, MODE_FULL, out_dtype, s);
   }
   if (rc) {

@@ -184,7 +184,9 @@ struct embed_args {
   long long vocab;
   const void *wpe;
   long long n_pos;
-  const void *base;  // gather_reduce: [ntok, d] added after the reduce, or null
+  const void *base;  // [ntok, d] in the output dtype, or null.  gather_reduce: added after the reduce; hit source (scone_embed_base):
+                     // the dense base row of every position, in the place of wte[tok] -- a launch on a slice of the batch offsets it
+                     // with tok / pos / out
   int reduce;
   int mode;           // SCONE_MODE_* (honoured by the wave kernels)
   int fused;          // decode-size batch: match inside the lookup kernel (k_embed_fused)
@@ -276,6 +278,8 @@ __global__ __launch_bounds__(256) void k_embed(const embed_args a) {
     if constexpr (MODE != MODE_PARTIAL) {
       if (tok_ok) load_vec<OutT, VEC>(wte + (long long)tokv * d + (long long)v * VEC, bw);
       if (pos_ok) load_vec<OutT, VEC>(wpe + (long long)posv * d + (long long)v * VEC, bp);
+      // base and out are indexed by `group`, relative to tok_begin (as the caller's slices are); the full lookup has tok_begin = 0.
+      // out == base is fine: this lane loads the vector it stores below, and no other lane touches it
       if (bas && active) load_vec<OutT, VEC>(bas + group * (long long)d + (long long)v * VEC, bb);
     }
 

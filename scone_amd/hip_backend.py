@@ -442,6 +442,85 @@ class SconeTable:
             self._check(rc, "scone_embed_varlen")
         return out
 
+    def _base_args(self, who: str, ntok: int, base: torch.Tensor, wpe: Optional[torch.Tensor],
+                   out_dtype: Optional[torch.dtype], out: Optional[torch.Tensor], shape) -> Tuple[torch.dtype, torch.Tensor]:
+        """Validation shared by :meth:`embed_base` and :meth:`embed_base_varlen`: ``(out_dtype, out)``."""
+        if not isinstance(base, torch.Tensor):
+            raise ValueError(f"{who}: base must be a tensor")
+        if out_dtype is None:
+            out_dtype = base.dtype
+        if out_dtype not in _DT:
+            raise ValueError(f"{who}: out_dtype must be float32, float16 or bfloat16")
+        if not (base.is_cuda and base.is_contiguous() and base.dtype == out_dtype and base.dim() >= 2
+                and base.shape[-1] == self.dim and base.numel() == ntok * self.dim):
+            raise ValueError(f"{who}: base must be a contiguous {out_dtype} tensor of {ntok} rows of {self.dim} on {self.device}")
+        if wpe is not None and not (wpe.is_cuda and wpe.is_contiguous() and wpe.dtype == out_dtype and wpe.dim() == 2
+                                    and wpe.shape[1] == self.dim):
+            raise ValueError(f"wpe must be a contiguous [*, {self.dim}] {out_dtype} tensor on {self.device}")
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=self.device)
+        else:
+            assert out.is_cuda and out.is_contiguous() and out.dtype == out_dtype and out.numel() == ntok * self.dim
+        return out_dtype, out
+
+    def embed_base(self, tok: torch.Tensor, base: torch.Tensor, *, wpe: Optional[torch.Tensor] = None,
+                   position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",
+                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_embed_base``: :meth:`embed` onto a DENSE base -> ``[B, T, d]``,
+        ``out[b, t] = (base[b, t] + reduce_k row_k) + wpe[pos[b, t]]``.  ``base`` (``[B, T, d]`` or ``[B * T, d]``, contiguous,
+        on the device, in the output dtype) takes the place of ``wte[tok]``; token ids serve the match only (no vocabulary).
+        On a ``longest_suffix`` table a matched f-gram replaces the base row.  ``out=base`` is the in-place call and is passed
+        through untouched; an ``out`` that overlaps ``base`` in any other way is refused (``ValueError``)."""
+        if not (tok.dim() == 2 and tok.dtype == torch.int32 and tok.is_cuda and tok.is_contiguous()):
+            tok = self._tok(tok)
+        B, T = tok.shape
+        out_dtype, out = self._base_args("embed_base", B * T, base, wpe, out_dtype, out, (B, T, self.dim))
+        if position_ids is not None:
+            position_ids = position_ids.to(device=self.device, dtype=torch.int32).expand(B, T).contiguous()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = L.lib().scone_embed_base(self._h, tok.data_ptr(), B, T, base.data_ptr(), None if wpe is None else wpe.data_ptr(),
+                                      0 if wpe is None else wpe.shape[0],
+                                      None if position_ids is None else position_ids.data_ptr(), _REDUCE[reduce],
+                                      out.data_ptr(), _DT[out_dtype], stream)
+        if rc != L.OK:
+            self._check(rc, "scone_embed_base")
+        return out
+
+    def embed_base_varlen(self, tok: torch.Tensor, cu_seqlens, base: torch.Tensor, *, wpe: Optional[torch.Tensor] = None,
+                          position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",
+                          out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_embed_base_varlen``: :meth:`embed_varlen` onto a dense ``base [total, d]`` -> ``[total, d]`` (see
+        :meth:`embed_base`; ``cu_seqlens`` as in :meth:`embed_varlen`)."""
+        if tok.dim() != 1:
+            raise ValueError("embed_base_varlen takes the packed token ids as a 1-D tensor [total]")
+        if not (tok.dtype == torch.int32 and tok.is_cuda and tok.is_contiguous()):
+            tok = tok.to(device=self.device, dtype=torch.int32).contiguous()
+        total = tok.shape[0]
+        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+            if not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                    and cu_seqlens.numel() >= 1):
+                raise ValueError("a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+            cu = cu_seqlens
+        else:
+            cu = torch.from_numpy(check_cu_seqlens(cu_seqlens, total)).to(self.device)
+        n_seqs = cu.numel() - 1
+        out_dtype, out = self._base_args("embed_base_varlen", total, base, wpe, out_dtype, out, (total, self.dim))
+        if position_ids is not None:
+            position_ids = position_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            if position_ids.numel() != total:
+                raise ValueError(f"position_ids must hold one position per packed token ({total})")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = L.lib().scone_embed_base_varlen(self._h, tok.data_ptr(), cu.data_ptr(), n_seqs, total, base.data_ptr(),
+                                             None if wpe is None else wpe.data_ptr(), 0 if wpe is None else wpe.shape[0],
+                                             None if position_ids is None else position_ids.data_ptr(), _REDUCE[reduce],
+                                             out.data_ptr(), _DT[out_dtype], stream)
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"scone_embed_base_varlen: {L.lib().scone_last_error(self._h).decode()} "
+                                       f"[{L.lib().scone_strerror(rc).decode()}]")
+        if rc != L.OK:
+            self._check(rc, "scone_embed_base_varlen")
+        return out
+
     def embed_prefetch(self, tok: torch.Tensor, tokens_ready: bool = False) -> None:
         """``scone_embed_prefetch``: start the pinned-host prefetch pipeline for ``tok`` (int32 ``[B, T]`` on the device: pass the
         very tensor the later :meth:`embed` gets) behind the current stream -- or, ``tokens_ready=True``, right away (the tokens

@@ -287,19 +287,27 @@ class EmbeddingCache:
         projection folded into the table.  ``check=True`` synchronises and raises
         ``IndexError`` for token / position ids outside ``wte`` / ``wpe``.
 
-        ``base [B, T, d]`` instead of ``wte`` / ``wpe``: a dense tensor the caller has already computed (the
-        ``inputs_embeds`` of language_model.py:239-243, say) -- ``out = base + reduce_k row(f_gram_k)``, one rounding to
-        ``out_dtype`` (default: ``base``'s dtype); the match produces CSR lists and ``scone_gather_reduce`` consumes them.
+        ``base [B, T, d]`` instead of ``wte``: a dense tensor the caller has already computed (the ``inputs_embeds`` of
+        language_model.py:239-243, a tensor-parallel or scaled ``wte``, an adapter's output) --
+        ``out = (base + reduce_k row(f_gram_k)) + wpe[position_ids]``, one rounding to ``out_dtype`` (default: ``base``'s
+        dtype).  On a ``lookup_mode="cover"`` cache this is ``scone_embed_base``: the launches of the ``wte`` road, stream-
+        ordered, with ``wpe=``, ``position_ids=``, ``check=``, ``out=`` (``out=base`` updates the tensor in place; any other
+        overlap is refused) and ``cu_seqlens=`` (``base`` is then ``[total, d]``, on the device).  ``base`` on the device,
+        contiguous and already in ``out_dtype`` is read where it is; anything else is converted first.  ``wte=`` together
+        with ``base=`` raises ``ValueError``.  On a ``lookup_mode="longest_suffix"`` cache ``base=`` keeps its earlier road
+        and result -- the match produces CSR lists of ALL covering f-grams, ``scone_gather_reduce`` adds their mean to
+        ``base`` -- and takes none of ``wpe=`` / ``position_ids=`` / ``out=`` / ``cu_seqlens=`` (``ValueError``); the
+        paper's lookup onto a dense base (a matched f-gram replaces the base row) is ``cache.table.embed_base``.
 
         ``cu_seqlens [n + 1]``: ``input_ids`` is a PACKED batch ``[total]`` (sequences back to back, sequence ``s`` =
         ``input_ids[cu_seqlens[s]:cu_seqlens[s + 1]]``, see :meth:`pack_sequences`) -> ``[total, d]``; every token gets what
         its sequence alone would give it, without padding (``scone_embed_varlen``; new here).  ``position_ids [total]``
         defaults to the place inside the sequence.  Host ``cu_seqlens`` are validated (``ValueError``), a device tensor is
-        trusted.  Not together with ``base=``.
+        trusted.
         """
+        if base is not None:
+            return self._embed_tokens_base(input_ids, base, reduce, wte, wpe, position_ids, out_dtype, out, check, cu_seqlens)
         if cu_seqlens is not None:
-            if base is not None:
-                raise ValueError("cu_seqlens= (a packed batch) cannot be combined with base=")
             tok = torch.as_tensor(input_ids)
             if tok.dim() != 1:
                 raise ValueError("with cu_seqlens=, input_ids must be the 1-D packed token ids [total]")
@@ -312,24 +320,70 @@ class EmbeddingCache:
             if check and table.status() & 1:
                 raise IndexError("index out of range in self")
             return result
-        if base is not None:
-            if wte is not None or wpe is not None or position_ids is not None or out is not None:
-                raise ValueError("base= replaces wte / wpe / position_ids (and takes no out=)")
-            table = self.to_device()
-            tok = torch.as_tensor(input_ids)
-            if tok.dim() == 1:
-                tok = tok.unsqueeze(0)
-            B, T = tok.shape
-            if tuple(base.shape) != (B, T, self.embedding_dim):
-                raise ValueError(f"base must be [{B}, {T}, {self.embedding_dim}]")
-            if out_dtype is None:
-                out_dtype = base.dtype
-            offsets, ids = table.match_csr(tok)
-            return table.gather_reduce(offsets, ids, reduce, base=base.reshape(B * T, self.embedding_dim),
-                                       out_dtype=out_dtype).view(B, T, self.embedding_dim)
         table = self.to_device()
         result = table.embed(torch.as_tensor(input_ids), wte=wte, wpe=wpe, position_ids=position_ids, reduce=reduce,
                              out_dtype=out_dtype, out=out)
+        if check and table.status() & 1:
+            raise IndexError("index out of range in self")
+        return result
+
+    def _embed_tokens_base(self, input_ids, base, reduce, wte, wpe, position_ids, out_dtype, out, check, cu_seqlens):
+        """``embed_tokens(base=...)``; every ``ValueError`` here is raised before any device work."""
+        d = self.embedding_dim
+        if wte is not None:
+            raise ValueError("base= takes the place of wte=: pass one of them")
+        if not isinstance(base, torch.Tensor):
+            raise ValueError("base= must be a tensor")
+        tok = torch.as_tensor(input_ids)
+        packed = cu_seqlens is not None
+        if self.lookup_mode != "cover":
+            # the earlier road, kept as it was: the CSR lists are the covering lists whatever the mode
+            if packed or wpe is not None or position_ids is not None or out is not None:
+                raise ValueError("on a lookup_mode='longest_suffix' cache base= takes no wpe= / position_ids= / out= / cu_seqlens= "
+                                 "(it adds the mean of ALL covering f-grams to base); the paper's lookup onto a dense base is "
+                                 "cache.table.embed_base / embed_base_varlen")
+            if tok.dim() == 1:
+                tok = tok.unsqueeze(0)
+            B, T = tok.shape
+            if tuple(base.shape) != (B, T, d):
+                raise ValueError(f"base must be [{B}, {T}, {d}]")
+            if out_dtype is None:
+                out_dtype = base.dtype
+            table = self.to_device()
+            offsets, ids = table.match_csr(tok)
+            return table.gather_reduce(offsets, ids, reduce, base=base.reshape(B * T, d), out_dtype=out_dtype).view(B, T, d)
+        if packed:
+            if tok.dim() != 1:
+                raise ValueError("with cu_seqlens=, input_ids must be the 1-D packed token ids [total]")
+            total = tok.shape[0]
+            if tuple(base.shape) != (total, d):
+                raise ValueError(f"with cu_seqlens=, base= must be [{total}, {d}] (one row per packed token)")
+            if not base.is_cuda:
+                raise ValueError("with cu_seqlens=, base= must be a tensor on the device")
+            if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda):
+                from scone_amd.hip_backend import check_cu_seqlens
+                cu_seqlens = check_cu_seqlens(cu_seqlens, total)      # before any device work
+        else:
+            if tok.dim() == 1:
+                tok = tok.unsqueeze(0)
+            if tok.dim() != 2:
+                raise ValueError("token ids must be [T] or [B, T]")
+            B, T = tok.shape
+            if tuple(base.shape) != (B, T, d):
+                raise ValueError(f"base must be [{B}, {T}, {d}]")
+        if out_dtype is None:
+            out_dtype = base.dtype
+        table = self.to_device()
+        if not (base.is_cuda and base.device == table.device and base.is_contiguous() and base.dtype == out_dtype):
+            if out is not None and out is base:
+                raise ValueError(f"out=base needs a contiguous {out_dtype} base= on {table.device}")
+            base = base.to(device=table.device, dtype=out_dtype).contiguous()
+        if packed:
+            result = table.embed_base_varlen(tok, cu_seqlens, base, wpe=wpe, position_ids=position_ids, reduce=reduce,
+                                             out_dtype=out_dtype, out=out)
+        else:
+            result = table.embed_base(tok, base, wpe=wpe, position_ids=position_ids, reduce=reduce, out_dtype=out_dtype, out=out)
+            result = result.view(B, T, d)
         if check and table.status() & 1:
             raise IndexError("index out of range in self")
         return result
