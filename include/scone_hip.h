@@ -51,10 +51,24 @@ enum {
   SCONE_FMT_I8 = 2,  /* [N,d] int8 + scales[N] half (per row)           row_bytes d+2     */
   SCONE_FMT_I4 = 3,  /* [N,d/2] offset-binary nibbles (elem 2k = low)   row_bytes d/2+2*d/128
                         + scales[N,d/128] half (per 128-group)                            */
-  SCONE_FMT_BF16 = 4 /* [N,d] bfloat16 (the upper half of the fp32), no scales, d % 8 == 0   row_bytes 2d
+  SCONE_FMT_BF16 = 4,/* [N,d] bfloat16 (the upper half of the fp32), no scales, d % 8 == 0   row_bytes 2d
                         fp32 rows are stored with IEEE round-to-nearest-even (NaN stays a quiet NaN); a row reads
                         back as bits << 16, so every lookup equals the fp32 lookup of the dequantised table
                         bit for bit.  Appended: the values above and SCONE_ABI_VERSION are unchanged.   */
+  SCONE_FMT_MXFP4 = 5 /* OCP microscaling MXFP4, d % 128 == 0                              row_bytes d/2+d/32
+                        [N,d/2] E2M1 nibbles (elem 2k = low nibble of byte k, the order of INT4 here and of torch's
+                        float4_e2m1fn_x2): s m2 m1 m0, magnitude codes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6, bit 3 the sign, no
+                        inf / NaN code, 0x8 is -0
+                        + scales[N,d/32] uint8 E8M0, one per 32 consecutive elements, logical order in upload / download:
+                        X in 0..254 means 2^(X-127) (X = 0: the fp32 subnormal 2^-127), X = 255 makes the block NaN.
+                        value = fp32(elem) * fp32(2^(X-127)), ONE IEEE fp32 product: exact for every (code, X) but the
+                        large codes at X >= 253, which overflow to +-inf.  Rows are summed as acc += value, so every
+                        lookup equals the fp32 lookup of the dequantised table bit for bit.
+                        fp32 rows are stored block by block by the OCP MX v1.0 rule: a block with a NaN or +-inf gets
+                        X = 255 (nibbles: the sign bits); else amax = max|v|, amax == 0 -> X = 127 and signed zeros, else
+                        X = clamp(floor(log2(amax)) - 2 + 127, 0, 254), and each v / 2^(X-127) goes to the nearest E2M1
+                        magnitude, ties to the even code, above 6 to 6, sign kept (|v - dq(v)| <= amax / 4).
+                        Appended: the values above and SCONE_ABI_VERSION are unchanged.   */
 };
 enum {
   SCONE_PLACE_HBM = 0,        /* rows in device memory                                              */
@@ -185,7 +199,12 @@ int scone_table_store_f32(scone_handle *h, const float *d_rows_f32, uint64_t row
 int scone_table_store_f32_ids(scone_handle *h, const float *d_rows_f32, const int64_t *d_ids,
                               uint64_t nrows, scone_stream_t stream);
 /* Counter-based synthetic rows (bench / full-size tests); any row can be
- * recomputed on the host (oracle/ref_port.py synth_*). */
+ * recomputed on the host (oracle/ref_port.py synth_*).
+ * SCONE_FMT_MXFP4 (restated in tests/mxfp4_fixture.py): with hash32 the lowbias32 finaliser and
+ * base(c) = hash32((uint32)c + 0x9E3779B9 * (uint32)(c >> 32)) ^ seed, payload dword w of row g is
+ * hash32(base(g) + w) -- the words INT4 gets -- and the scale byte of block b of row g is
+ * E - 1 + (hash32(base(g * (d/32) + b) + 0x51ED27) >> 8) % 3, E = the exponent field of base_scale clamped to
+ * [1, 253]: within +-1 of floor(log2(base_scale)) + 127. */
 int scone_table_fill_synthetic(scone_handle *h, uint32_t seed, float base_scale,
                                scone_stream_t stream);
 /* Row gather: out[i,:] = dequantised row d_ids[i] as fp32

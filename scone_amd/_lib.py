@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("SCONE_HIP_LIB") or os.path.join(_HERE, "csrc", "libsc
 
 ABI_VERSION = 2
 
-FMT_F32, FMT_F16, FMT_I8, FMT_I4, FMT_BF16 = 0, 1, 2, 3, 4
+FMT_F32, FMT_F16, FMT_I8, FMT_I4, FMT_BF16, FMT_MXFP4 = 0, 1, 2, 3, 4, 5
 PLACE_HBM, PLACE_PINNED_HOST = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 MODE_COVER, MODE_LONGEST_SUFFIX = 0, 1

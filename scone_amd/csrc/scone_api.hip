@@ -169,6 +169,10 @@ static bool payload_geometry(const scone_cfg &c, size_t *payload, size_t *scale_
       if (d % SCONE_I4_GROUP) return false;
       *payload = d / 2, *scale_bytes = 2 * (d / SCONE_I4_GROUP);
       return true;
+    case SCONE_FMT_MXFP4:
+      if (d % 128) return false;
+      *payload = d / 2, *scale_bytes = d / SCONE_MX_BLOCK;
+      return true;
     default: return false;
   }
 }
@@ -306,7 +310,7 @@ extern "C" int scone_create(const scone_cfg *cfg, scone_handle **out) {
   }
   if (cfg->dim > 0) {
     if (!payload_geometry(h->cfg, &h->row_payload_bytes, &h->scale_bytes_per_row)) {
-      h->err = "scone_create: dim not compatible with table_fmt (F32 %4, F16 %8, I8 %16, I4 %128, BF16 %8)";
+      h->err = "scone_create: dim not compatible with table_fmt (F32 %4, F16 %8, I8 %16, I4 %128, BF16 %8, MXFP4 %128)";
       rc = SCONE_EINVAL;
       goto fail;
     }

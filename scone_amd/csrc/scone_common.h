@@ -114,6 +114,31 @@ __host__ __device__ inline uint32_t scone_hash32(uint32_t x) {
 // logical order [N, d/128]; every kernel indexes through this function.
 __host__ __device__ inline int scone_i4_scale_slot(int g, int d) { return d == 1024 ? (((g & 3) << 1) | (g >> 2)) : g; }
 
+// MXFP4 block scales (one E8M0 byte per 32 elements), physical order inside a row's scale array.  d = 1024: a lane of the
+// wave-per-token kernel owns 8 elements of block b = lane / 4 (first 512-element segment) and 8 of block 16 + lane / 4
+// (second segment); stored next to each other they are ONE 16-bit load per row and lane (slot = 2 (b mod 16) + b / 16).
+// Every other d: logical order.  Hidden from the C ABI exactly as the INT4 slots are.
+__host__ __device__ inline int scone_mx_scale_slot(int b, int d) { return d == 1024 ? (((b & 15) << 1) | (b >> 4)) : b; }
+#define SCONE_MX_BLOCK 32
+// The format's definition in plain arithmetic (the lookup kernels use the hardware convert, scone_gather_impl.h mx_accumulate,
+// which the exhaustive GPU test holds to this): E2M1 nibble -> fp32, E8M0 byte -> fp32 factor, value = their IEEE product.
+__host__ __device__ inline float scone_mx_elem(uint32_t nib) {
+  const uint32_t m = nib & 7u;  // 0, 0.5, then (1 + m0 / 2) 2^((m >> 1) - 1): bits (m << 22) + (126 << 23)
+  const uint32_t bits = (m < 2u ? (m ? 0x3F000000u : 0u) : (m << 22) + 0x3F000000u) | ((nib & 8u) << 28);
+  union { uint32_t u; float f; } c;
+  c.u = bits;
+  return c.f;
+}
+__host__ __device__ inline float scone_mx_scale(uint32_t x) {
+  union { uint32_t u; float f; } c;
+  c.u = x == 255u ? 0x7FC00000u : (x ? x << 23 : 0x00400000u);  // NaN block; 2^(X-127); X = 0: the subnormal 2^-127
+  return c.f;
+}
+// either format's slot (scone_table.hip reorders uploads / downloads through it)
+__host__ __device__ inline int scone_scale_slot(int fmt, int g, int d) {
+  return fmt == SCONE_FMT_MXFP4 ? scone_mx_scale_slot(g, d) : scone_i4_scale_slot(g, d);
+}
+
 // Where a local row lives: rows [0, hot) in HBM, the rest (if any) in mapped pinned host memory.
 struct scone_row_store {
   uint8_t *hot;
@@ -174,7 +199,7 @@ struct scone_handle {
   void *rows;        // payload rows in HBM: local rows [0, hot_local)
   void *rows_host;   // payload rows in pinned host DRAM: local rows [hot_local, local_rows) (or null)
   uint64_t hot_local;
-  void *scales;      // I8: half[rows]; I4: half[rows, d/128]
+  void *scales;      // I8: half[rows]; I4: half[rows, d/128]; MXFP4: uint8[rows, d/32]
   size_t row_payload_bytes;
   size_t scale_bytes_per_row;
   uint64_t local_rows;

@@ -118,11 +118,14 @@ __device__ __forceinline__ void bf16_accumulate_column(const uint32_t *w, float 
 
 // sum / K of a lane's elements.  fp32 / fp16 / bf16 tables can hold anything (a sum may overflow, be subnormal, inf or NaN;
 // a bf16 row spans fp32's whole exponent range): the full IEEE quotient -- the `else` below is theirs, and a new format
-// belongs there unless its sums are provably in range.  A sum of INT8 / INT4 rows is +0 or a multiple of 2^-24 far below
+// belongs there unless its sums are provably in range (MXFP4 spans fp32's whole range too: the full quotient, in the form that
+// lets the zero sums of that format pass, scone_mean_div_of_sum).  A sum of INT8 / INT4 rows is +0 or a multiple of 2^-24 far below
 // overflow, where the short form IS the IEEE quotient (scone_mean_div.h).
 template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const int n, const int k) {
   if constexpr (FMT == SCONE_FMT_I8 || FMT == SCONE_FMT_I4)
     scone_mean_div_in_range(acc, n, k);
+  else if constexpr (FMT == SCONE_FMT_MXFP4)
+    scone_mean_div_of_sum(acc, n, k);  // the full quotient; acc is a sum started at +0, and zero sums are common in this format
   else
     scone_mean_div(acc, n, k);
 }
@@ -136,8 +139,8 @@ template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const in
 template <int FMT, int D> struct wave_geom {
   static constexpr int EPL = D / 64;  // elements per lane
   static constexpr int NSEG = (D + 511) / 512;
-  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_BF16, "unknown table format");
-  static constexpr int BPE4 = FMT == SCONE_FMT_F32 ? 16 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 8 : FMT == SCONE_FMT_I8 ? 4 : 2;  // bytes per 4 elements (last arm: INT4)
+  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_MXFP4, "unknown table format");
+  static constexpr int BPE4 = FMT == SCONE_FMT_F32 ? 16 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 8 : FMT == SCONE_FMT_I8 ? 4 : 2;  // bytes per 4 elements (last arm: INT4 and MXFP4)
   static constexpr int ROW_BYTES = D / 4 * BPE4;
   static constexpr int NBR = ROW_BYTES / 64;  // row bytes per lane
   static constexpr int seg_elems(int s) { return ((D - 512 * s) >= 512 ? 512 : (D - 512 * s)) / 64; }  // per lane
@@ -146,7 +149,7 @@ template <int FMT, int D> struct wave_geom {
   static constexpr int seg_row_words(int s) { return seg_elems(s) * BPE4 / 16; }
   static constexpr int seg_row_word0(int s) { return 8 * s * BPE4 / 16; }
   static constexpr bool OK = (D % 256 == 0) && (D <= 1280) && (seg_elems(NSEG - 1) * BPE4 % 16 == 0) &&
-                             (FMT != SCONE_FMT_I4 || SCONE_I4_GROUP % 8 == 0);
+                             (FMT != SCONE_FMT_I4 || SCONE_I4_GROUP % 8 == 0) && (FMT != SCONE_FMT_MXFP4 || SCONE_MX_BLOCK % 8 == 0);
 };
 
 // waves per SIMD to ask of the register allocator: rows in flight (NC x NBR/4) + wte/wpe/out words +
@@ -178,7 +181,7 @@ template <int FMT, int D> struct wave_geom {
 // Switches for A/B builds: SCONE_HIOCC_MASK (bit FMT), SCONE_HIOCC_SLACK_CUT (registers taken off the occupancy
 // estimate of the variant).
 #ifndef SCONE_HIOCC_MASK
-#define SCONE_HIOCC_MASK 31  // bit FMT: all five formats (bf16, bit 4, has fp16's geometry and gains what fp16 gains)
+#define SCONE_HIOCC_MASK 63  // bit FMT: all six formats (bf16, bit 4, has fp16's geometry and gains what fp16 gains; MXFP4, bit 5, INT4's)
 #endif
 #ifndef SCONE_HIOCC_SLACK_CUT
 #define SCONE_HIOCC_SLACK_CUT 8
@@ -198,13 +201,17 @@ template <int FMT, typename OutT, int D, int MAXN, bool FIXED_POS, bool HIOCC = 
   static constexpr int NC = MAXN * (MAXN + 1) / 2;
   static constexpr int KL = NC;  // rows in flight
   static constexpr int NWO = wave_geom<FMT, D>::EPL * (int)sizeof(OutT) / 4;
-  // INT4 also holds one group-scale word per (row, segment) in flight
-  static constexpr int EST = KL * (wave_geom<FMT, D>::NBR / 4) + (FMT == SCONE_FMT_I4 ? KL * (D == 1024 ? 1 : wave_geom<FMT, D>::NSEG) : 0) +
+  // INT4 also holds one group-scale word per (row, segment) in flight; MXFP4 its block-scale bytes in the same places (at
+  // d = 1024 one 16-bit word per row) and otherwise INT4's registers: the payload words are the same, the decode keeps
+  // fewer temporaries (no ev / od halves, no sc / 16), so INT4's terms below are an upper bound for it
+  static constexpr bool NIB = FMT == SCONE_FMT_I4 || FMT == SCONE_FMT_MXFP4;
+  static constexpr int EST = KL * (wave_geom<FMT, D>::NBR / 4) + (NIB ? KL * (D == 1024 ? 1 : wave_geom<FMT, D>::NSEG) : 0) +
                              (FIXED_POS && !HIOCC ? 4 : 3) * NWO +
                              wave_geom<FMT, D>::EPL + SCONE_WAVE_SLACK - (HIOCC && MAXN <= 3 && sizeof(OutT) == 2 ? SCONE_HIOCC_SLACK_CUT : 0) +
                              (HIOCC && sizeof(OutT) == 4 ? 8 : 0) +  // fp32 output: the LDS read-back of the position row is twice as wide
-                             (FMT == SCONE_FMT_I4 && !HIOCC ? 8 : 0) +  // INT4 at 6 waves spills 44 B/lane on the K >= 4 paths
-                             (MAXN >= 4 ? (FMT == SCONE_FMT_I4 ? 24 : 8) : 0) +  // the 10-way switch keeps more addresses live
+                             (NIB && !HIOCC ? 8 : 0) +  // INT4 at 6 waves spills 44 B/lane on the K >= 4 paths
+                             (MAXN >= 4 ? (NIB ? 24 : 8) : 0) +  // the 10-way switch keeps more addresses live
+                             (FMT == SCONE_FMT_MXFP4 && MAXN >= 4 && !FIXED_POS ? 8 : 0) +  // MXFP4, per-token position rows, fp16 out: 48 B of scratch at 6 waves
                              (std::is_same<OutT, __hip_bfloat16>::value ? 4 : 0);  // round-to-nearest-even by hand
   static constexpr int ALLOC = (EST + 7) / 8 * 8;
 #ifdef SCONE_FORCE_WAVES
@@ -312,6 +319,15 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
           scw[k][s] = reinterpret_cast<const unsigned short *>(scales_v)[lr * (D / SCONE_I4_GROUP) +
                                                                          scone_i4_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_I4_GROUP, D)];
         }
+      } else if constexpr (FMT == SCONE_FMT_MXFP4) {
+        if constexpr (D == 1024) {
+          // scone_mx_scale_slot: the lane's two block scales (segment 0: block lane / 4, segment 1: block 16 + lane / 4) are
+          // the two bytes of ONE 16-bit word
+          scw[k][s] = s == 0 ? reinterpret_cast<const unsigned short *>(scales_v)[lr * (D / SCONE_MX_BLOCK / 2) + (lane >> 2)] : 0u;
+        } else {
+          scw[k][s] = reinterpret_cast<const uint8_t *>(scales_v)[lr * (D / SCONE_MX_BLOCK) +
+                                                                  scone_mx_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_MX_BLOCK, D)];
+        }
       } else {
         scw[k][s] = 0;
       }
@@ -351,6 +367,11 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
           sc = __half2float(__ushort_as_half((unsigned short)(s == 0 ? (scw[k][0] & 0xFFFFu) : (scw[k][0] >> 16))));
         else
           sc = __half2float(__ushort_as_half((unsigned short)scw[k][s]));
+      } else if constexpr (FMT == SCONE_FMT_MXFP4) {
+        if constexpr (D == 1024)
+          sc = mx_scale_operand(s == 0 ? (scw[k][0] & 0xFFu) : (scw[k][0] >> 8));
+        else
+          sc = mx_scale_operand(scw[k][s]);
       }
       // acc[seg_acc(s) ..] += dequant(raw[k][seg words]); exact products, list order (see accumulate<>)
 #pragma unroll
@@ -373,6 +394,10 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
             const int q = (int)(w << (24 - 8 * b)) >> 24;
             acc[G::seg_acc(s) + 4 * i + b] = fmaf(sc, (float)q, acc[G::seg_acc(s) + 4 * i + b]);
           }
+        } else if constexpr (FMT == SCONE_FMT_MXFP4) {
+          const int a = G::seg_acc(s) + 8 * i;  // the word summed before this one: the lane's previous 8 elements, or the last 8 of the row before
+          const int b = a > 0 ? a - 2 : EPL - 2;
+          mx_accumulate(w, sc, &acc[a], a > 0 || k > 0, acc[b], acc[b + 1]);
         } else {
           static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
           i4_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
@@ -768,7 +793,7 @@ int launch_wave(scone_handle *h, const embed_args &a, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 // Any embedding dim that is a multiple of 8 (2048, 4096, ... -- the specialised kernel above covers
 // 768 / 1024 / 1280).  Same wave-per-token scheme and the same arithmetic; the row is walked in UNITS
-// of 8 elements (INT8 8 B, fp16 / bf16 16 B, fp32 32 B, INT4 4 B per lane; 16 B of fp16 output), lane l
+// of 8 elements (INT8 8 B, fp16 / bf16 16 B, fp32 32 B, INT4 / MXFP4 4 B per lane; 16 B of fp16 output), lane l
 // taking units l, l+64, ...: every access is a contiguous run, every 64-B sector is touched whole.
 // K stays a compile-time constant (switch outside the unit loop), so the K loads of a unit are issued
 // back to back.
@@ -778,8 +803,8 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
                                             int reduce, const uint8_t *wte_row,  // (no __restrict__: out == base, see embed_token)
                                             const uint8_t *__restrict__ wpe_row, uint8_t *out_row, uint32_t lane) {
   constexpr int U = 8;                                  // elements per unit
-  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_BF16, "unknown table format");
-  constexpr int RW = FMT == SCONE_FMT_F32 ? 8 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 4 : FMT == SCONE_FMT_I8 ? 2 : 1;  // row words per unit (last arm: INT4)
+  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_MXFP4, "unknown table format");
+  constexpr int RW = FMT == SCONE_FMT_F32 ? 8 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 4 : FMT == SCONE_FMT_I8 ? 2 : 1;  // row words per unit (last arm: INT4 and MXFP4)
   constexpr int OW = U * (int)sizeof(OutT) / 4;         // output words per unit
   constexpr int OPW = pack_io<OutT>::PER_WORD;
   constexpr int KK = K > 0 ? K : 1;
@@ -816,6 +841,8 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
       scw[k] = 0;
       if constexpr (FMT == SCONE_FMT_I4)
         scw[k] = reinterpret_cast<const unsigned short *>(scales_v)[lrs[k] * (d / SCONE_I4_GROUP) + scone_i4_scale_slot((u * U) / SCONE_I4_GROUP, d)];
+      if constexpr (FMT == SCONE_FMT_MXFP4)
+        scw[k] = reinterpret_cast<const uint8_t *>(scales_v)[lrs[k] * (d / SCONE_MX_BLOCK) + scone_mx_scale_slot((u * U) / SCONE_MX_BLOCK, d)];
     }
     float acc[U];
 #pragma unroll
@@ -829,6 +856,7 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
     for (int k = 0; k < (FMT == SCONE_FMT_BF16 ? 0 : K); ++k) {
       float sc = sc8[k];
       if constexpr (FMT == SCONE_FMT_I4) sc = __half2float(__ushort_as_half((unsigned short)scw[k]));
+      if constexpr (FMT == SCONE_FMT_MXFP4) sc = mx_scale_operand(scw[k]);
 #pragma unroll
       for (int i = 0; i < RW; ++i) {
         const uint32_t w = raw[k][i];
@@ -845,6 +873,8 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
             const int q = (int)(w << (24 - 8 * b)) >> 24;
             acc[4 * i + b] = fmaf(sc, (float)q, acc[4 * i + b]);
           }
+        } else if constexpr (FMT == SCONE_FMT_MXFP4) {
+          mx_accumulate(w, sc, acc, k > 0, acc[6], acc[7]);
         } else {
           static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
           i4_accumulate(w, sc, acc);
@@ -995,6 +1025,9 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
       } else if constexpr (FMT == SCONE_FMT_I4) {
         sc = __half2float(reinterpret_cast<const __half *>(scales_v)[lr * (D / SCONE_I4_GROUP) +
                                                                       scone_i4_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_I4_GROUP, D)]);
+      } else if constexpr (FMT == SCONE_FMT_MXFP4) {
+        sc = mx_scale_operand(reinterpret_cast<const uint8_t *>(scales_v)[lr * (D / SCONE_MX_BLOCK) +
+                                                                          scone_mx_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_MX_BLOCK, D)]);
       }
 #pragma unroll
       for (int i = 0; i < G::seg_row_words(s); ++i) {
@@ -1013,6 +1046,8 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
             const int q = (int)(w << (24 - 8 * b)) >> 24;
             acc[G::seg_acc(s) + 4 * i + b] = fmaf(sc, (float)q, acc[G::seg_acc(s) + 4 * i + b]);
           }
+        } else if constexpr (FMT == SCONE_FMT_MXFP4) {
+          mx_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
         } else {
           static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
           i4_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);

@@ -33,6 +33,7 @@ int launch_fmt(scone_handle *h, const embed_args &a, int src, int mode, int out_
     case SCONE_FMT_I8: return launch_i8(h, a, src, mode, out_dtype, s);
     case SCONE_FMT_I4: return launch_i4(h, a, src, mode, out_dtype, s);
     case SCONE_FMT_BF16: return launch_bf16(h, a, src, mode, out_dtype, s);
+    case SCONE_FMT_MXFP4: return launch_mxfp4(h, a, src, mode, out_dtype, s);
     default: return scone_fail(h, SCONE_EINVAL, "unknown table_fmt");
   }
 }
@@ -59,10 +60,11 @@ int check_mode(scone_handle *h, const char *who) {
 }
 
 // decode-size batches are launch-bound: one fused launch (k_embed_fused) instead of match + gather
-// (INT4 has no specialised kernel at d = 768 / 1280: a row segment would be narrower than one 16-B access)
+// (INT4 has no specialised kernel at d = 768 / 1280: a row segment would be narrower than one 16-B access; MXFP4 has INT4's
+// payload geometry and follows the same rule)
 bool scone_embed_takes_one_launch(const scone_handle *h, long long BT) {
   return BT <= h->fused_max_tokens && (h->cfg.dim == 768 || h->cfg.dim == 1024 || h->cfg.dim == 1280) &&
-         !(h->cfg.table_fmt == SCONE_FMT_I4 && h->cfg.dim != 1024);
+         !((h->cfg.table_fmt == SCONE_FMT_I4 || h->cfg.table_fmt == SCONE_FMT_MXFP4) && h->cfg.dim != 1024);
 }
 
 #ifdef SCONE_PROBE_PERM

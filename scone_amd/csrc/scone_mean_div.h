@@ -20,7 +20,13 @@
 // of 2^-24 below 2^55.  (The test costs the INT8 headline 0.6 % of its time; the quantised kernels do
 // not need it.)
 //
-// Plain C: tests/mean_div_host.c includes this file and holds both functions to x / k on the CPU (tests/test_mean_div_cpu.py).
+// scone_mean_div_of_sum: scone_mean_div for an x that is a list-order sum started at +0.  Such a sum is never -0 (+0 + -0 = +0,
+// and nothing added to a non-zero sum gives -0), and for x = +0 the three instructions give +0, the quotient; so a zero
+// element need not send its lane through the true division.  For a table whose rows hold many zeros -- MXFP4: code 0 is one
+// of 8 magnitudes, so with K = 2 rows a lane of 16 elements holds a zero sum in every fifth token -- that is the difference
+// between the division being rare and being the rule.  Every other x is judged exactly as scone_mean_div judges it.
+//
+// Plain C: tests/mean_div_of_sum_host.c holds it to x / k for every x but -0.  tests/mean_div_host.c includes this file and holds both functions to x / k on the CPU (tests/test_mean_div_cpu.py).
 #pragma once
 
 #include <math.h>
@@ -54,6 +60,26 @@ SCONE_MEAN_DIV_FN void scone_mean_div(float *acc, const int n, const int k) {
     const float a0 = fabsf(acc[e] * y);
     // "q0 is a normal number" (one class test on the device); NaN fails the first comparison
     if (!(a0 >= SCONE_MEAN_DIV_MIN_NORMAL && a0 < INFINITY)) fast = 0;
+  }
+  if (fast) {
+    scone_mean_div_in_range(acc, n, k);
+  } else {
+#pragma unroll
+    for (int e = 0; e < n; ++e) acc[e] = acc[e] / kf;
+  }
+}
+
+SCONE_MEAN_DIV_FN void scone_mean_div_of_sum(float *acc, const int n, const int k) {
+  const float kf = (float)k;
+  // the quotient is a normal number for certain, and x y with it, when 2^-125 kf <= |x| < inf (y = RN(1 / kf) >= (1 - 2^-24) / kf):
+  // one threshold for all of the lane's elements instead of a product per element (x / k in [2^-126, 2^-125) takes the true
+  // division too, which is always right)
+  const float lo = kf * 2.3509887e-38f;  // 2^-125 kf
+  int fast = 1;
+#pragma unroll
+  for (int e = 0; e < n; ++e) {
+    const float a = fabsf(acc[e]);
+    if (!((a >= lo && a < INFINITY) || a == 0.0f)) fast = 0;  // (a sum is never -0)
   }
   if (fast) {
     scone_mean_div_in_range(acc, n, k);

@@ -7,7 +7,8 @@
 //
 // Row formats are this library's own (the reference stores fp32 only); the numpy
 // statement of the quantisers is oracle/ref_port.py quantize_i8 / quantize_i4; that of the bf16 rounding is
-// tests/bf16_fixture.py to_bf16_bits.
+// tests/bf16_fixture.py to_bf16_bits, that of the MXFP4 quantiser tests/mxfp4_fixture.py quantize (the format itself:
+// include/scone_hip.h).
 #include "scone_common.h"
 
 #include <type_traits>
@@ -69,6 +70,33 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
       o[e] = (int8_t)(int)q;
     }
     if (lane == 0) scales[lr] = sh;
+  } else if (FMT == SCONE_FMT_MXFP4) {
+    // 128 elements per pass: lane l holds elements 2l, 2l + 1 (one payload byte), 16 lanes share a block of 32.
+    // OCP MX v1.0: a NaN / inf in the block -> X = 255; else X = max(0, exponent field of amax - 2) (amax = 0: 127), which is
+    // clamp(floor(log2 amax) - 2 + 127, 0, 254) -- a subnormal amax has field 0, FLT_MAX 254 -> 252.  q = |v| 2^(127-X) is exact
+    // (a power-of-two scaling; where it underflows it is far below the first midpoint), and the comparisons below are
+    // round-to-nearest with ties to the even code: 0.25 -> 0, 0.75 -> 1.0, 1.25 -> 1.0, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4.
+    const int nb = d / SCONE_MX_BLOCK;
+    uint8_t *o = st.row(lr);
+    uint8_t *sc = reinterpret_cast<uint8_t *>(scales);
+    for (int grp = 0; grp < d / 128; ++grp) {
+      const uint32_t ua = __float_as_uint(x[grp * 128 + 2 * lane]), ub = __float_as_uint(x[grp * 128 + 2 * lane + 1]);
+      uint32_t m = max(ua & 0x7FFFFFFFu, ub & 0x7FFFFFFFu);
+      for (int sh = 8; sh >= 1; sh >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, sh, 64));
+      const uint32_t X = m >= 0x7F800000u ? 255u : (m == 0u ? 127u : ((m >> 23) > 2u ? (m >> 23) - 2u : 0u));
+      uint32_t nib[2];
+      const uint32_t uu[2] = {ua, ub};
+      for (int k = 0; k < 2; ++k) {
+        uint32_t code = 0;
+        if (X != 255u) {
+          const float q = __uint_as_float(uu[k] & 0x7FFFFFFFu) * __uint_as_float((254u - X) << 23);
+          code = (q > 0.25f) + (q >= 0.75f) + (q > 1.25f) + (q >= 1.75f) + (q > 2.5f) + (q >= 3.5f) + (q > 5.0f);
+        }
+        nib[k] = code | ((uu[k] >> 31) << 3);
+      }
+      o[grp * 64 + lane] = (uint8_t)(nib[0] | (nib[1] << 4));
+      if ((lane & 15) == 0) sc[lr * nb + scone_mx_scale_slot(grp * 4 + (lane >> 4), d)] = (uint8_t)X;
+    }
   } else {  // I4: groups of 128, two elements per lane per group
     const int ng = d / SCONE_I4_GROUP;
     uint8_t *o = st.row(lr);
@@ -126,6 +154,17 @@ __global__ __launch_bounds__(256) void k_fill_synth(unsigned long long row_begin
       scales[lr * ng + scone_i4_scale_slot(grp, d)] = synth_scale(seed, g * (unsigned long long)ng + grp, base_scale);
     continue;
   }
+  if (FMT == SCONE_FMT_MXFP4) {  // the recipe is stated in include/scone_hip.h (scone_table_fill_synthetic)
+    const int nw = d / 8, nb = d / SCONE_MX_BLOCK;
+    uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
+    for (int w = lane; w < nw; w += 64) o[w] = scone_hash32(base + (uint32_t)w);
+    uint32_t e = (__float_as_uint(base_scale) >> 23) & 0xFFu;
+    e = e < 1u ? 1u : (e > 253u ? 253u : e);
+    for (int b = lane; b < nb; b += 64)
+      reinterpret_cast<uint8_t *>(scales)[lr * nb + scone_mx_scale_slot(b, d)] =
+          (uint8_t)(e - 1u + (scone_hash32(synth_row_base(seed, g * (unsigned long long)nb + b) + 0x51ED27u) >> 8) % 3u);
+    continue;
+  }
   const int nw = d / 4;
   const __half sh = synth_scale(seed, g, base_scale);
   const float sf = __half2float(sh);
@@ -181,6 +220,15 @@ __global__ __launch_bounds__(256) void k_gather_rows(scone_row_store st, const _
     const int8_t *x = reinterpret_cast<const int8_t *>(st.row(lr));
     const float sf = __half2float(scales[lr]);
     for (int e = lane; e < d; e += 64) o[e] = (float)x[e] * sf;
+  } else if (FMT == SCONE_FMT_MXFP4) {
+    const uint8_t *x = st.row(lr);
+    const uint8_t *sc = reinterpret_cast<const uint8_t *>(scales) + lr * (unsigned long long)(d / SCONE_MX_BLOCK);
+    for (int b = lane; b < d / 2; b += 64) {
+      const float sf = scone_mx_scale(sc[scone_mx_scale_slot((2 * b) / SCONE_MX_BLOCK, d)]);
+      const uint8_t v = x[b];
+      o[2 * b] = scone_mx_elem(v & 0xFu) * sf;
+      o[2 * b + 1] = scone_mx_elem(v >> 4) * sf;
+    }
   } else {
     const uint8_t *x = st.row(lr);
     const int ng = d / SCONE_I4_GROUP;
@@ -202,6 +250,7 @@ int dispatch_fmt(int fmt, F &&f) {
     case SCONE_FMT_I8: f(std::integral_constant<int, SCONE_FMT_I8>()); return 0;
     case SCONE_FMT_I4: f(std::integral_constant<int, SCONE_FMT_I4>()); return 0;
     case SCONE_FMT_BF16: f(std::integral_constant<int, SCONE_FMT_BF16>()); return 0;
+    case SCONE_FMT_MXFP4: f(std::integral_constant<int, SCONE_FMT_MXFP4>()); return 0;
     default: return -1;
   }
 }
@@ -217,36 +266,58 @@ void table_modified(scone_handle *h) {
   if (h->stage) scone_stage_destroy(h);
 }
 
-// logical <-> physical order of INT4 group scales (scone_i4_scale_slot), in place, one thread per row
-__global__ __launch_bounds__(256) void k_i4_scales_reorder(__half *__restrict__ s, unsigned long long n_rows, int ng, int d,
-                                                           int to_physical) {
+// logical <-> physical order of a row's scales (INT4 group scales, 2 bytes: scone_i4_scale_slot; MXFP4 block scales,
+// 1 byte: scone_mx_scale_slot), in place, one thread per row
+template <typename T>
+__global__ __launch_bounds__(256) void k_scales_reorder(T *__restrict__ s, unsigned long long n_rows, int ng, int d, int fmt,
+                                                        int to_physical) {
   const unsigned long long r = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_rows || ng > 16) return;
-  __half v[16];
+  if (r >= n_rows || ng > 32) return;
+  T v[32];
   for (int g = 0; g < ng; ++g) v[g] = s[r * ng + g];
   for (int g = 0; g < ng; ++g) {
     if (to_physical)
-      s[r * ng + scone_i4_scale_slot(g, d)] = v[g];
+      s[r * ng + scone_scale_slot(fmt, g, d)] = v[g];
     else
-      s[r * ng + g] = v[scone_i4_scale_slot(g, d)];
+      s[r * ng + g] = v[scone_scale_slot(fmt, g, d)];
   }
 }
 
-bool i4_scales_permuted(const scone_handle *h) {
-  return h->cfg.table_fmt == SCONE_FMT_I4 && scone_i4_scale_slot(1, h->cfg.dim) != 1;
+bool scales_permuted(const scone_handle *h) {
+  return (h->cfg.table_fmt == SCONE_FMT_I4 || h->cfg.table_fmt == SCONE_FMT_MXFP4) &&
+         scone_scale_slot(h->cfg.table_fmt, 1, h->cfg.dim) != 1;
+}
+int scales_per_row(const scone_handle *h) {
+  return h->cfg.table_fmt == SCONE_FMT_MXFP4 ? h->cfg.dim / SCONE_MX_BLOCK : h->cfg.dim / SCONE_I4_GROUP;
 }
 
-void i4_scales_reorder_host(uint16_t *s, uint64_t n_rows, int ng, int d, bool to_physical) {
-  uint16_t v[16];
+void scales_reorder_device(scone_handle *h, void *s, uint64_t nrows, int to_physical, hipStream_t st) {
+  const dim3 grid((unsigned)((nrows + 255) / 256));
+  if (h->cfg.table_fmt == SCONE_FMT_MXFP4)
+    hipLaunchKernelGGL(k_scales_reorder<uint8_t>, grid, dim3(256), 0, st, (uint8_t *)s, (unsigned long long)nrows,
+                       scales_per_row(h), h->cfg.dim, h->cfg.table_fmt, to_physical);
+  else
+    hipLaunchKernelGGL(k_scales_reorder<uint16_t>, grid, dim3(256), 0, st, (uint16_t *)s, (unsigned long long)nrows,
+                       scales_per_row(h), h->cfg.dim, h->cfg.table_fmt, to_physical);
+}
+
+template <typename T> void scales_reorder_host_t(T *s, uint64_t n_rows, int ng, int d, int fmt, bool to_physical) {
+  T v[32];
   for (uint64_t r = 0; r < n_rows; ++r) {
     for (int g = 0; g < ng; ++g) v[g] = s[r * ng + g];
     for (int g = 0; g < ng; ++g) {
       if (to_physical)
-        s[r * ng + scone_i4_scale_slot(g, d)] = v[g];
+        s[r * ng + scone_scale_slot(fmt, g, d)] = v[g];
       else
-        s[r * ng + g] = v[scone_i4_scale_slot(g, d)];
+        s[r * ng + g] = v[scone_scale_slot(fmt, g, d)];
     }
   }
+}
+void scales_reorder_host(const scone_handle *h, void *s, uint64_t n_rows, bool to_physical) {
+  if (h->cfg.table_fmt == SCONE_FMT_MXFP4)
+    scales_reorder_host_t(reinterpret_cast<uint8_t *>(s), n_rows, scales_per_row(h), h->cfg.dim, h->cfg.table_fmt, to_physical);
+  else
+    scales_reorder_host_t(reinterpret_cast<uint16_t *>(s), n_rows, scales_per_row(h), h->cfg.dim, h->cfg.table_fmt, to_physical);
 }
 
 }  // namespace
@@ -277,9 +348,8 @@ extern "C" int scone_table_upload(scone_handle *h, const void *rows, const void 
     uint8_t *dst = reinterpret_cast<uint8_t *>(h->scales) + lr * h->scale_bytes_per_row;
     SCONE_HIP(h, hipMemcpyAsync(dst, scales, nrows * h->scale_bytes_per_row,
                                 src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    if (i4_scales_permuted(h)) {  // the ABI speaks the logical group order; the table keeps scone_i4_scale_slot's
-      hipLaunchKernelGGL(k_i4_scales_reorder, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, (__half *)dst,
-                         (unsigned long long)nrows, h->cfg.dim / SCONE_I4_GROUP, h->cfg.dim, 1);
+    if (scales_permuted(h)) {  // the ABI speaks the logical order; the table keeps scone_i4_scale_slot's / scone_mx_scale_slot's
+      scales_reorder_device(h, dst, nrows, 1, s);
       SCONE_HIP(h, hipGetLastError());
     }
   }
@@ -312,16 +382,14 @@ extern "C" int scone_table_download(scone_handle *h, void *rows, void *scales, u
     SCONE_HIP(h, hipMemcpyAsync(scales, reinterpret_cast<const uint8_t *>(h->scales) + lr * h->scale_bytes_per_row,
                                 nrows * h->scale_bytes_per_row,
                                 dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    if (i4_scales_permuted(h) && dst_is_device) {  // back to the logical group order
-      hipLaunchKernelGGL(k_i4_scales_reorder, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, (__half *)scales,
-                         (unsigned long long)nrows, h->cfg.dim / SCONE_I4_GROUP, h->cfg.dim, 0);
+    if (scales_permuted(h) && dst_is_device) {  // back to the logical order
+      scales_reorder_device(h, scales, nrows, 0, s);
       SCONE_HIP(h, hipGetLastError());
     }
   }
   if (!dst_is_device) {
     SCONE_HIP(h, hipStreamSynchronize(s));
-    if (i4_scales_permuted(h))
-      i4_scales_reorder_host(reinterpret_cast<uint16_t *>(scales), nrows, h->cfg.dim / SCONE_I4_GROUP, h->cfg.dim, false);
+    if (scales_permuted(h)) scales_reorder_host(h, scales, nrows, false);
   }
   return SCONE_OK;
 }

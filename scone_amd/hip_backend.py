@@ -13,13 +13,14 @@ from . import _lib as L
 _FMT = {"fp32": L.FMT_F32, "float32": L.FMT_F32, "f32": L.FMT_F32,
         "fp16": L.FMT_F16, "float16": L.FMT_F16, "f16": L.FMT_F16,
         "int8": L.FMT_I8, "i8": L.FMT_I8, "int4": L.FMT_I4, "i4": L.FMT_I4,
-        "bf16": L.FMT_BF16, "bfloat16": L.FMT_BF16}
+        "bf16": L.FMT_BF16, "bfloat16": L.FMT_BF16, "mxfp4": L.FMT_MXFP4}
 _PLACE = {"hbm": L.PLACE_HBM, "pinned_host": L.PLACE_PINNED_HOST}
 _REDUCE = {"mean": L.REDUCE_MEAN, "sum": L.REDUCE_SUM}
 _MODE = {"cover": L.MODE_COVER, "longest_suffix": L.MODE_LONGEST_SUFFIX}
 _DT = {torch.float32: L.DT_F32, torch.float16: L.DT_F16, torch.bfloat16: L.DT_BF16}
 
 I4_GROUP = 128
+MX_BLOCK = 32   # MXFP4: one E8M0 scale byte per 32 elements
 
 
 def format_code(fmt) -> int:
@@ -28,13 +29,13 @@ def format_code(fmt) -> int:
     try:
         return _FMT[str(fmt).lower()]
     except KeyError:
-        raise ValueError(f"unknown table format {fmt!r} (fp32, fp16, int8, int4, bf16)") from None
+        raise ValueError(f"unknown table format {fmt!r} (fp32, fp16, int8, int4, bf16, mxfp4)") from None
 
 
 def row_bytes(fmt: int, d: int) -> int:
     """Algorithmic bytes per table row."""
     return {L.FMT_F32: 4 * d, L.FMT_F16: 2 * d, L.FMT_I8: d + 2,
-            L.FMT_I4: d // 2 + 2 * (d // I4_GROUP), L.FMT_BF16: 2 * d}[fmt]
+            L.FMT_I4: d // 2 + 2 * (d // I4_GROUP), L.FMT_BF16: 2 * d, L.FMT_MXFP4: d // 2 + d // MX_BLOCK}[fmt]
 
 
 class SconeError(RuntimeError):
@@ -246,7 +247,17 @@ class SconeTable:
 
     # -- table ------------------------------------------------------------------
     def upload(self, rows, scales=None, row0: int = 0) -> None:
-        """Raw rows already in the table format (numpy host arrays or device tensors)."""
+        """Raw rows already in the table format (numpy host arrays or device tensors).  MXFP4: payload bytes ``[n, d/2]`` and
+        E8M0 scale bytes ``[n, d/32]`` in logical block order; ``torch.float4_e2m1fn_x2`` / ``torch.float8_e8m0fnu`` tensors
+        (an existing MX checkpoint) are taken as their bytes."""
+        if self.fmt == L.FMT_MXFP4:
+            rows, scales = (x.view(torch.uint8) if isinstance(x, torch.Tensor) and x.dtype != torch.uint8 and x.element_size() == 1
+                            else x for x in (rows, scales))
+            for x, width in ((rows, self.payload_bytes()), (scales, self.scales_per_row())):
+                if x is None or tuple(x.shape[1:]) != (width,) or str(x.dtype).rsplit(".", 1)[-1] != "uint8":
+                    raise ValueError(f"mxfp4 upload takes uint8 rows [n, {self.payload_bytes()}] and uint8 scales [n, {self.scales_per_row()}]")
+            if isinstance(rows, torch.Tensor) and not rows.is_cuda:
+                rows, scales = rows.numpy(), (scales.numpy() if isinstance(scales, torch.Tensor) else scales)
         is_dev = isinstance(rows, torch.Tensor)
         if is_dev:
             assert rows.is_cuda and rows.is_contiguous()
@@ -256,7 +267,7 @@ class SconeTable:
             rows = np.ascontiguousarray(rows)
             nrows, rp = rows.shape[0], rows.ctypes.data_as(C.c_void_p)
             if scales is not None:
-                scales = np.ascontiguousarray(scales, dtype=np.float16)
+                scales = np.ascontiguousarray(scales, dtype=self.scales_dtype())
             sp = scales.ctypes.data_as(C.c_void_p) if scales is not None else None
         with torch.cuda.device(self.device):
             rc = L.lib().scone_table_upload(self._h, rp, sp, int(row0), int(nrows), int(is_dev), _stream())
@@ -264,22 +275,27 @@ class SconeTable:
 
     def payload_bytes(self) -> int:
         return {L.FMT_F32: 4 * self.dim, L.FMT_F16: 2 * self.dim, L.FMT_I8: self.dim, L.FMT_I4: self.dim // 2,
-                L.FMT_BF16: 2 * self.dim}[self.fmt]
+                L.FMT_BF16: 2 * self.dim, L.FMT_MXFP4: self.dim // 2}[self.fmt]
 
     def scales_per_row(self) -> int:
-        return {L.FMT_F32: 0, L.FMT_F16: 0, L.FMT_I8: 1, L.FMT_I4: self.dim // I4_GROUP, L.FMT_BF16: 0}[self.fmt]
+        return {L.FMT_F32: 0, L.FMT_F16: 0, L.FMT_I8: 1, L.FMT_I4: self.dim // I4_GROUP, L.FMT_BF16: 0,
+                L.FMT_MXFP4: self.dim // MX_BLOCK}[self.fmt]
+
+    def scales_dtype(self):
+        """numpy dtype of a scale: fp16 (INT8 / INT4), one E8M0 byte (MXFP4)."""
+        return np.dtype(np.uint8) if self.fmt == L.FMT_MXFP4 else np.dtype(np.float16)
 
     def download(self, row0: int, nrows: int, rows: Optional[np.ndarray] = None,
                  scales: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-        """Raw payload rows ``uint8 [nrows, payload_bytes]`` and fp16 scales of global rows ``row0 ..`` -- into ``rows`` /
+        """Raw payload rows ``uint8 [nrows, payload_bytes]`` and scales (fp16; MXFP4: E8M0 bytes, logical order) of global rows ``row0 ..`` -- into ``rows`` /
         ``scales`` when given (contiguous host arrays of those shapes, e.g. slices of a memory-mapped file)."""
         spr = self.scales_per_row()
         if rows is None:
             rows = np.empty((nrows, self.payload_bytes()), dtype=np.uint8)
         if scales is None and spr:
-            scales = np.empty((nrows, spr), dtype=np.float16)
+            scales = np.empty((nrows, spr), dtype=self.scales_dtype())
         assert rows.shape == (nrows, self.payload_bytes()) and rows.dtype == np.uint8 and rows.flags["C_CONTIGUOUS"]
-        assert not spr or (scales.shape == (nrows, spr) and scales.dtype == np.float16 and scales.flags["C_CONTIGUOUS"])
+        assert not spr or (scales.shape == (nrows, spr) and scales.dtype == self.scales_dtype() and scales.flags["C_CONTIGUOUS"])
         if not spr:
             scales = None
         with torch.cuda.device(self.device):
@@ -811,7 +827,7 @@ class SconeTable:
         self._check(rc, "scone_shard_cols_build_frag")
 
     def scale_bytes(self) -> int:
-        return 2 * self.scales_per_row()
+        return (1 if self.fmt == L.FMT_MXFP4 else 2) * self.scales_per_row()      # E8M0 bytes; fp16 otherwise
 
     def shard_head_version(self) -> int:
         """Counter bumped by every change of the replicated head (buffers that start with the head's scales are refilled)."""

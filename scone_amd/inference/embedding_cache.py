@@ -5,7 +5,7 @@ constructor, attributes and method signatures (``cache_embeddings``,
 ``get_embeddings``, ``get_token_embeddings``, ``save``, ``load``), the same
 exceptions and the same on-disk formats.  Host attributes (``embeddings`` dict /
 ``memory_mapped_embeddings``) are kept as the reference keeps them; every *lookup*
-is served from a device copy of the table (fp32 / fp16 / bf16 / INT8 / INT4 rows in HBM
+is served from a device copy of the table (fp32 / fp16 / bf16 / INT8 / INT4 / MXFP4 rows in HBM
 or in pinned host memory) by the kernels behind ``include/scone_hip.h``.  There is
 no CPU fallback for lookups.
 
@@ -28,7 +28,10 @@ class EmbeddingCache:
 
     Extra keyword-only arguments select the device representation:
         table_format: "fp32" (reference-exact), "fp16", "int8", "int4", "bf16" (the exact two-byte home of a table
-                      whose embeddings were produced in bfloat16; lookups equal the fp32 ones of those rows bit for bit).
+                      whose embeddings were produced in bfloat16; lookups equal the fp32 ones of those rows bit for bit),
+                      "mxfp4" (OCP microscaling: E2M1 elements, one E8M0 scale per 32; embedding_dim % 128 == 0; lookups
+                      equal the fp32 ones of the dequantised rows bit for bit; an existing MX checkpoint goes in through
+                      ``SconeTable.upload(rows_uint8, scales_uint8)``).
         placement:    "hbm" or "pinned_host" (rows >= hot_rows stay in host DRAM, read over PCIe).
         hot_rows:     with "pinned_host", the head of the table (ids are frequency-ordered) kept in HBM.
         stage_tokens: with "pinned_host": 0 = rows are read in place over PCIe by the lookup kernel; > 0 =
@@ -520,7 +523,7 @@ class EmbeddingCache:
         else:                                             # closed-form vocabulary: its parameters are the keys
             meta["vocabulary"] = {"kind": type(ex).__name__, "n_rows": len(ex), "vocab": getattr(ex, "vocab", None)}
         sections["rows"] = ("uint8", (b - a, table.payload_bytes()))
-        sections["scales"] = ("float16", (b - a, spr))
+        sections["scales"] = (table.scales_dtype().name if hasattr(table, "scales_dtype") else "float16", (b - a, spr))
         if with_index:
             sb, ub, bb = table.index_blob_sizes()
             sections["index_slots"] = ("uint8", (sb,))
