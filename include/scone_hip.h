@@ -532,6 +532,38 @@ int scone_ipc_event_record(scone_handle *h, void *event, scone_stream_t stream);
 int scone_ipc_event_wait(scone_handle *h, void *event, scone_stream_t stream);
 int scone_ipc_push(scone_handle *h, void *d_dst, const void *d_src, uint64_t bytes, int32_t copy_engine, scone_stream_t stream);
 
+/* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
+ * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
+ * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.
+ *   for j in [0, n_sel), p = d_sel[j]:  out[j,:] = exactly the bits the full lookup over the same tokens writes to its row p
+ * d_cu_seqlens == NULL: the tokens are a rectangle, rows of T tokens (total_tokens % T == 0; n_seqs ignored) -- scone_embed's
+ * batch.  d_cu_seqlens given: the packed stream of scone_embed_varlen ([n_seqs + 1] int32 on the device), T ignored.  All rules
+ * of the full lookup hold: the id list in the reference's order, the sequential fp32 sum, the IEEE mean, zero-fill for K = 0,
+ * (base row + fg) + wpe, both lookup modes, the row_begin / row_end ownership rule with divisor = full K.
+ * Everything per OUTPUT is indexed by j, not by p: d_base is [n_sel, d] in out_dtype and row j is the base of output j (the
+ * caller holds embeddings of the selected tokens only); d_pos is int32 [n_sel], or NULL for the place of p inside its sequence;
+ * d_out is [n_sel, d].  d_wte / vocab: the base row is wte[tok[p]] as in scone_embed.  d_wte and d_base together: SCONE_EINVAL;
+ * neither: the term is omitted.  d_out == d_base is the defined in-place call, any other overlap of the two [n_sel, d] ranges
+ * returns SCONE_EINVAL.  d_sel may be unsorted and may repeat positions: each j is written on its own.  For d_sel[j] outside
+ * [0, total_tokens) nothing is read, row j is NOT written and SCONE_ST_BAD_TOKEN is raised.  Whatever d_cu_seqlens holds, no
+ * token outside d_tok[0, total_tokens) is read.
+ * n_sel comes from the host: ONE launch of ceil(n_sel / 4) workgroups for every n_sel that fits a grid, at every d % 8 == 0
+ * and every table format (d = 768 / 1024 / 1280 specialised, any other dim -- and INT4 / MXFP4 at 768 / 1280 -- walked in
+ * units of 8 elements); no workspace, no lock, no synchronisation; thread-safe like scone_embed.  n_sel == 0 or
+ * total_tokens == 0 (or a packed batch of n_seqs == 0): a no-op.
+ * What it is NOT for: n_sel comparable to total_tokens.  A wavefront probes every candidate window of its token, like the
+ * one-launch road of scone_embed; above that road's measured crossover (32768 tokens) the full lookup, one probe per window,
+ * is the faster way to most of a batch.
+ * SCONE_EINVAL (scone_last_error names the reason): a null d_tok / d_sel / d_out, negative sizes, total_tokens > 2^31 - 1, a
+ * rectangle with T <= 0 or total_tokens % T != 0, a bad reduce / out_dtype, d_wte with vocab <= 0, d_wpe with n_pos <= 0,
+ * d % 8 != 0, a pinned-host table created with stage_tokens > 0 (tables read in place from pinned host memory work). */
+int scone_embed_select(scone_handle *h, const int32_t *d_tok, int64_t total_tokens, int32_t T,
+                       const int32_t *d_cu_seqlens, int32_t n_seqs,
+                       const int32_t *d_sel, int64_t n_sel,
+                       const void *d_wte, int64_t vocab, const void *d_base,
+                       const void *d_wpe, int64_t n_pos, const int32_t *d_pos,
+                       int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

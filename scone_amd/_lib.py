@@ -79,6 +79,7 @@ SIGNATURES = {
     "scone_embed_varlen": (C.c_int, [_P, _P, _P, _I32, _I64, _P, _I64, _P, _I64, _P, _I32, _P, _I32, _P]),
     "scone_embed_base": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
     "scone_embed_base_varlen": (C.c_int, [_P, _P, _P, _I32, _I64, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
+    "scone_embed_select": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
     "scone_embed_prefetch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "scone_reserve": (C.c_int, [_P, _I64]),
     "scone_set_cu_reserve": (C.c_int, [_P, _I32]),

@@ -13,6 +13,7 @@
 // one token, each lane 16-byte vectors of every row).  Accumulation is sequential in the reference's list order in
 // fp32 everywhere, so results do not depend on the launch geometry.
 #include "scone_gather_impl.h"
+#include "scone_embed_select.h"
 #ifdef SCONE_PROBE_PERM
 #include <cstdlib>
 #endif
@@ -486,6 +487,62 @@ static int embed_packed(scone_handle *h, const int32_t *d_tok, const int32_t *d_
     r.out = reinterpret_cast<uint8_t *>(a.out) + (size_t)main_tok * h->cfg.dim * esz;
     if (a.base) r.base = reinterpret_cast<const uint8_t *>(a.base) + (size_t)main_tok * h->cfg.dim * esz;  // dense base: same rows as out
     rc = launch_fmt(h, r, SRC_HITS, MODE_FULL, out_dtype, s);
+  }
+  if (rc) {
+    scone_prof_abort(h);
+    return rc;
+  }
+  return scone_prof_end(h, s);
+}
+
+// The fused lookup at chosen positions only (scone_embed_select.h): one launch of ceil(n_sel / 4) workgroups, no workspace, no
+// lock, no synchronisation -- thread-safe like the one-launch road of scone_embed.
+extern "C" int scone_embed_select(scone_handle *h, const int32_t *d_tok, int64_t total_tokens, int32_t T,
+                                  const int32_t *d_cu_seqlens, int32_t n_seqs, const int32_t *d_sel, int64_t n_sel,
+                                  const void *d_wte, int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos,
+                                  const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream) {
+  int rc = need_table(h, "scone_embed_select: handle has no table (dim == 0)");
+  if (rc) return rc;
+  if (total_tokens < 0 || n_sel < 0 || (d_cu_seqlens && n_seqs < 0))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: negative total_tokens, n_sel or n_seqs");
+  if (total_tokens > 0x7FFFFFFFll) return scone_fail(h, SCONE_EINVAL, "scone_embed_select: total_tokens above 2^31 - 1");
+  if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM) return scone_fail(h, SCONE_EINVAL, "scone_embed_select: bad reduce");
+  if (out_dtype != SCONE_DT_F32 && out_dtype != SCONE_DT_F16 && out_dtype != SCONE_DT_BF16)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: bad out_dtype");
+  if (h->cfg.dim % 8 != 0) return scone_fail(h, SCONE_EINVAL, "scone_embed_select: needs d % 8 == 0");
+  if (h->cfg.stage_tokens && h->rows_host)
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: not for stage_tokens > 0 (the staging pipeline prefetches whole batches; "
+                                       "tables read in place from pinned host memory work)");
+  if (!d_cu_seqlens && total_tokens > 0 && (T <= 0 || total_tokens % T != 0))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: a rectangle needs T > 0 and total_tokens % T == 0");
+  if (d_wte && d_base) return scone_fail(h, SCONE_EINVAL, "scone_embed_select: d_wte and d_base are exclusive");
+  if ((d_wte && vocab <= 0) || (d_wpe && n_pos <= 0))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: wte/wpe given without vocab/n_pos");
+  if (n_sel == 0 || total_tokens == 0 || (d_cu_seqlens && n_seqs == 0)) return SCONE_OK;
+  if (!d_tok || !d_sel || !d_out) return scone_fail(h, SCONE_EINVAL, "scone_embed_select: null pointer (d_tok, d_sel and d_out are required)");
+  if (!scone_grid_fits(((unsigned long long)n_sel + 3) / 4, 256))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: too many selected positions for one launch");
+  if (d_base && base_overlaps_out(d_base, d_out, (unsigned long long)n_sel * h->cfg.dim * (out_dtype == SCONE_DT_F32 ? 4 : 2)))
+    return scone_fail(h, SCONE_EINVAL, "scone_embed_select: d_base overlaps d_out (only d_out == d_base, the in-place call, is defined)");
+  SCONE_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  select_args a = {};
+  fill_table_view(h, a.tv);
+  a.tok = d_tok, a.total = total_tokens, a.T = d_cu_seqlens ? 0 : T, a.cu = d_cu_seqlens, a.n_seqs = n_seqs;
+  a.sel = d_sel, a.n_sel = n_sel;
+  a.wte = d_wte, a.vocab = vocab, a.base = d_base, a.wpe = d_wpe, a.n_pos = n_pos, a.pos = d_pos;
+  a.reduce = reduce, a.mode = (int)h->cfg.lookup_mode, a.max_n = h->cfg.max_n;
+  a.zero_row = h->d_zero_row, a.out = d_out, a.status = h->d_status;
+  rc = scone_prof_begin(h, s);
+  if (rc) return rc;
+  switch (h->cfg.table_fmt) {
+    case SCONE_FMT_F32: rc = launch_select_f32(h, a, out_dtype, s); break;
+    case SCONE_FMT_F16: rc = launch_select_f16(h, a, out_dtype, s); break;
+    case SCONE_FMT_I8: rc = launch_select_i8(h, a, out_dtype, s); break;
+    case SCONE_FMT_I4: rc = launch_select_i4(h, a, out_dtype, s); break;
+    case SCONE_FMT_BF16: rc = launch_select_bf16(h, a, out_dtype, s); break;
+    case SCONE_FMT_MXFP4: rc = launch_select_mxfp4(h, a, out_dtype, s); break;
+    default: rc = scone_fail(h, SCONE_EINVAL, "unknown table_fmt");
   }
   if (rc) {
     scone_prof_abort(h);

@@ -537,6 +537,79 @@ class SconeTable:
             self._check(rc, "scone_embed_base_varlen")
         return out
 
+    def embed_select(self, tok: torch.Tensor, sel, *, cu_seqlens=None, wte: Optional[torch.Tensor] = None,
+                     base: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
+                     position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",
+                     out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_embed_select``: the fused lookup at CHOSEN positions only -> ``[n_sel, d]``.  ``out[j]`` holds exactly what
+        :meth:`embed` (``tok [B, T]``) or :meth:`embed_varlen` (``tok [total]`` with ``cu_seqlens=``) writes to its flattened
+        row ``sel[j]``, matched against the whole context -- one launch, for a decoding step's last tokens, a verify step's last
+        k, a prefill chunk.  ``sel`` (any order, repeats allowed) indexes the flattened tokens; ``base [n_sel, d]`` and
+        ``position_ids [n_sel]`` are per SELECTED row; ``wte`` and ``base`` are exclusive; ``out=base`` is the in-place call.
+        A ``sel`` entry outside ``[0, total)`` leaves its row unwritten and raises bit 0 of :meth:`status`.  Refusals of the
+        library come back as :class:`SconeInvalidArgument`."""
+        if cu_seqlens is None:
+            if not (tok.dim() == 2 and tok.dtype == torch.int32 and tok.is_cuda and tok.is_contiguous()):
+                tok = self._tok(tok)
+            total, T = tok.numel(), tok.shape[1]
+            cu, n_seqs = None, 0
+        else:
+            if tok.dim() != 1:
+                raise ValueError("embed_select with cu_seqlens takes the packed token ids as a 1-D tensor [total]")
+            if not (tok.dtype == torch.int32 and tok.is_cuda and tok.is_contiguous()):
+                tok = tok.to(device=self.device, dtype=torch.int32).contiguous()
+            total, T = tok.shape[0], 0
+            if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+                if not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                        and cu_seqlens.numel() >= 1):
+                    raise ValueError("a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+                cu = cu_seqlens
+            else:
+                cu = torch.from_numpy(check_cu_seqlens(cu_seqlens, total)).to(self.device)
+            n_seqs = cu.numel() - 1
+        if not isinstance(sel, torch.Tensor):
+            sel = torch.from_numpy(np.ascontiguousarray(np.asarray(sel, dtype=np.int64).astype(np.int32)))
+        if sel.dim() != 1:
+            raise ValueError("embed_select: sel must be a 1-D list of flattened token positions")
+        if not (sel.dtype == torch.int32 and sel.is_cuda and sel.is_contiguous()):
+            sel = sel.to(device=self.device, dtype=torch.int32).contiguous()
+        n_sel = sel.shape[0]
+        if wte is not None and base is not None:
+            raise SconeInvalidArgument("embed_select: wte and base are exclusive")
+        if base is not None:
+            out_dtype, out = self._base_args("embed_select", n_sel, base, wpe, out_dtype, out, (n_sel, self.dim))
+        else:
+            if out_dtype is None:
+                out_dtype = wte.dtype if wte is not None else (wpe.dtype if wpe is not None else torch.float32)
+            if out_dtype not in _DT:
+                raise ValueError("embed_select: out_dtype must be float32, float16 or bfloat16")
+            for name, w in (("wte", wte), ("wpe", wpe)):
+                if w is not None:
+                    if not (w.is_cuda and w.is_contiguous() and w.dtype == out_dtype and w.dim() == 2
+                            and w.shape[1] == self.dim):
+                        raise ValueError(f"{name} must be a contiguous [*, {self.dim}] {out_dtype} tensor on {self.device}")
+            if out is None:
+                out = torch.empty((n_sel, self.dim), dtype=out_dtype, device=self.device)
+            else:
+                assert out.is_cuda and out.is_contiguous() and out.dtype == out_dtype and out.numel() == n_sel * self.dim
+        if position_ids is not None:
+            position_ids = position_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            if position_ids.numel() != n_sel:
+                raise ValueError(f"position_ids must hold one position per selected row ({n_sel})")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = L.lib().scone_embed_select(self._h, tok.data_ptr(), total, T, None if cu is None else cu.data_ptr(), n_seqs,
+                                        sel.data_ptr(), n_sel, None if wte is None else wte.data_ptr(),
+                                        0 if wte is None else wte.shape[0], None if base is None else base.data_ptr(),
+                                        None if wpe is None else wpe.data_ptr(), 0 if wpe is None else wpe.shape[0],
+                                        None if position_ids is None else position_ids.data_ptr(), _REDUCE[reduce],
+                                        out.data_ptr(), _DT[out_dtype], stream)
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"scone_embed_select: {L.lib().scone_last_error(self._h).decode()} "
+                                       f"[{L.lib().scone_strerror(rc).decode()}]")
+        if rc != L.OK:
+            self._check(rc, "scone_embed_select")
+        return out
+
     def embed_prefetch(self, tok: torch.Tensor, tokens_ready: bool = False) -> None:
         """``scone_embed_prefetch``: start the pinned-host prefetch pipeline for ``tok`` (int32 ``[B, T]`` on the device: pass the
         very tensor the later :meth:`embed` gets) behind the current stream -- or, ``tokens_ready=True``, right away (the tokens

@@ -279,7 +279,8 @@ class EmbeddingCache:
     def embed_tokens(self, input_ids: torch.Tensor, *, reduce: str = "mean", wte: Optional[torch.Tensor] = None,
                      wpe: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                      out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
-                     check: bool = False, base: Optional[torch.Tensor] = None, cu_seqlens=None) -> torch.Tensor:
+                     check: bool = False, base: Optional[torch.Tensor] = None, cu_seqlens=None,
+                     select=None) -> torch.Tensor:
         """Fused lookup for ``input_ids [B, T]`` -> ``[B, T, d]``:
 
             out[b, t] = (wte[input_ids[b, t]] + reduce_k row(f_gram_k)) + wpe[position_ids[b, t]]
@@ -307,7 +308,18 @@ class EmbeddingCache:
         its sequence alone would give it, without padding (``scone_embed_varlen``; new here).  ``position_ids [total]``
         defaults to the place inside the sequence.  Host ``cu_seqlens`` are validated (``ValueError``), a device tensor is
         trusted.
+
+        ``select [n_sel]``: only the chosen positions of the flattened ``input_ids`` (``[B, T]``, or ``[total]`` with
+        ``cu_seqlens=``) are looked up -> ``[n_sel, d]``, row ``j`` holding exactly what the full call writes to its row
+        ``select[j]`` (``scone_embed_select``: one launch, matched against the whole context; any order, repeats allowed;
+        see :meth:`last_positions`).  ``base=`` (``[n_sel, d]``) and ``position_ids=`` (``[n_sel]``, default: the place
+        inside the sequence) are then per SELECTED row; ``check=`` works as before and also reports a ``select`` entry
+        outside the batch (its row is left unwritten).  On a ``lookup_mode="longest_suffix"`` cache ``base=`` with
+        ``select=`` is refused like the other extras there (``cache.table.embed_select`` is the paper's form).
         """
+        if select is not None:
+            return self._embed_tokens_select(input_ids, select, reduce, wte, wpe, position_ids, out_dtype, out, check, base,
+                                             cu_seqlens)
         if base is not None:
             return self._embed_tokens_base(input_ids, base, reduce, wte, wpe, position_ids, out_dtype, out, check, cu_seqlens)
         if cu_seqlens is not None:
@@ -390,6 +402,88 @@ class EmbeddingCache:
         if check and table.status() & 1:
             raise IndexError("index out of range in self")
         return result
+
+    def _embed_tokens_select(self, input_ids, select, reduce, wte, wpe, position_ids, out_dtype, out, check, base, cu_seqlens):
+        """``embed_tokens(select=...)``; every ``ValueError`` here is raised before any device work."""
+        d = self.embedding_dim
+        tok = torch.as_tensor(input_ids)
+        if cu_seqlens is not None:
+            if tok.dim() != 1:
+                raise ValueError("with cu_seqlens=, input_ids must be the 1-D packed token ids [total]")
+            if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda):
+                from scone_amd.hip_backend import check_cu_seqlens
+                cu_seqlens = check_cu_seqlens(cu_seqlens, tok.shape[0])
+        elif tok.dim() != 2:
+            raise ValueError("with select=, input_ids must be [B, T] (or [total] with cu_seqlens=)")
+        if isinstance(select, torch.Tensor):
+            sel = select
+            if sel.dtype.is_floating_point or sel.dtype == torch.bool:
+                raise ValueError("select= must hold integers")
+        else:
+            sel = np.asarray(select)
+            if sel.size and sel.dtype.kind not in "iu":
+                raise ValueError("select= must hold integers")
+            sel = torch.from_numpy(np.ascontiguousarray(sel.astype(np.int64).clip(-1, 2**31 - 1).astype(np.int32)))
+        if sel.dim() != 1:
+            raise ValueError("select= must be a 1-D list of flattened token positions")
+        n_sel = sel.shape[0]
+        if wte is not None and base is not None:
+            raise ValueError("base= takes the place of wte=: pass one of them")
+        if base is not None:
+            if self.lookup_mode != "cover":
+                raise ValueError("on a lookup_mode='longest_suffix' cache base= takes no select= (nor wpe= / position_ids= / out= / "
+                                 "cu_seqlens=); the paper's lookup at chosen positions onto a dense base is cache.table.embed_select")
+            if not isinstance(base, torch.Tensor):
+                raise ValueError("base= must be a tensor")
+            if tuple(base.shape) != (n_sel, d):
+                raise ValueError(f"with select=, base= must be [{n_sel}, {d}] (one row per selected position)")
+        if position_ids is not None and torch.as_tensor(position_ids).numel() != n_sel:
+            raise ValueError(f"with select=, position_ids= must hold one position per selected row ({n_sel})")
+        if out is not None and tuple(out.shape) != (n_sel, d):
+            raise ValueError(f"with select=, out= must be [{n_sel}, {d}]")
+        table = self.to_device()
+        if base is not None:
+            if out_dtype is None:
+                out_dtype = base.dtype
+            if not (base.is_cuda and base.device == table.device and base.is_contiguous() and base.dtype == out_dtype):
+                if out is not None and out is base:
+                    raise ValueError(f"out=base needs a contiguous {out_dtype} base= on {table.device}")
+                base = base.to(device=table.device, dtype=out_dtype).contiguous()
+        result = table.embed_select(tok, sel, cu_seqlens=cu_seqlens, wte=wte, base=base, wpe=wpe,
+                                    position_ids=None if position_ids is None else torch.as_tensor(position_ids),
+                                    reduce=reduce, out_dtype=out_dtype, out=out)
+        if check and table.status() & 1:
+            raise IndexError("index out of range in self")
+        return result
+
+    @staticmethod
+    def last_positions(cu_seqlens_or_shape, k: int = 1) -> torch.Tensor:
+        """Host helper beside :meth:`pack_sequences`: the flattened positions of the last ``min(k, len)`` tokens of every
+        sequence, in sequence order (ascending inside a sequence), empty sequences skipped -> int32 ``[n]`` on the CPU, ready
+        for ``embed_tokens(..., select=...)``.  The batch is named by its ``cu_seqlens`` (list / numpy / CPU tensor,
+        ``[n + 1]``) or, for a rectangle, by its shape ``(B, T)``."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("last_positions: k must be at least 1")
+        if isinstance(cu_seqlens_or_shape, (tuple, torch.Size)):
+            if len(cu_seqlens_or_shape) != 2:
+                raise ValueError("last_positions: a shape must be (B, T)")
+            B, T = (int(x) for x in cu_seqlens_or_shape)
+            if B < 0 or T < 0:
+                raise ValueError("last_positions: negative B or T")
+            cu = np.arange(B + 1, dtype=np.int64) * T
+        else:
+            from scone_amd.hip_backend import check_cu_seqlens
+            cu = np.asarray(cu_seqlens_or_shape.cpu() if isinstance(cu_seqlens_or_shape, torch.Tensor) else cu_seqlens_or_shape)
+            cu = check_cu_seqlens(cu, int(cu[-1]) if cu.ndim == 1 and cu.size else 0).astype(np.int64)
+        ends, lens = cu[1:], np.diff(cu)
+        take = np.minimum(lens, k)
+        n = int(take.sum())
+        if n > 2**31 - 1 or (cu.size and cu[-1] > 2**31 - 1):
+            raise ValueError("a batch holds at most 2^31 - 1 tokens")
+        first = np.repeat(ends - take, take)                              # first selected position of each sequence, per output
+        inside = np.arange(n, dtype=np.int64) - np.repeat(np.cumsum(take) - take, take)
+        return torch.from_numpy((first + inside).astype(np.int32))
 
     @staticmethod
     def pack_sequences(seqs) -> Tuple[torch.Tensor, torch.Tensor]:
