@@ -134,8 +134,9 @@ const char *scone_strerror(int code);
 int scone_create(const scone_cfg *cfg, scone_handle **out);
 void scone_destroy(scone_handle *h);
 const char *scone_last_error(const scone_handle *h);
-/* Sticky device-side status bits raised by kernels (bit 0: token outside the
- * base-embedding vocabulary, bit 1: f-gram id outside the table, bit 2: index
+/* Sticky device-side status bits raised by kernels (bit 0, SCONE_ST_BAD_TOKEN: a token id outside [0, vocab) of a given d_wte
+ * or a position id -- the caller's or the default one -- outside [0, n_pos) of a given d_wpe, see "Ids out of range" at
+ * scone_embed; also a scone_embed_select position outside the batch, bit 1: f-gram id outside the table, bit 2: index
  * full, bit 3: the cache of cold rows of a pinned-host lookup had no evictable slot for a row -- sized so that it cannot
  * happen; the affected tokens read a wrong row); synchronises the stream, returns the bits in *bits and clears them. */
 int scone_status(scone_handle *h, uint32_t *bits, scone_stream_t stream);
@@ -243,7 +244,21 @@ int scone_gather_reduce(scone_handle *h, const int32_t *d_offsets, const int32_t
  * Stream-ordered, no hidden synchronisation -- with ONE exception: the FIRST lookup (or scone_embed_prefetch) of a pinned-host
  * table with cfg.stage_tokens > 0 on a given caller stream synchronises that stream once, for ~1 ms: the staging pipeline
  * chooses its two side streams among six candidates by MEASURED overlap with the caller's stream (HIP multiplexes streams onto a
- * few hardware queues; side streams that share the caller's queue would serialise the prefetch behind the lookups). */
+ * few hardware queues; side streams that share the caller's queue would serialise the prefetch behind the lookups).
+ * Ids out of range (a padded batch: -1, -100, == vocab) are defined, never read out of bounds.  For every position p:
+ *   token term     wte[tok[p]] if 0 <= tok[p] < vocab, else a row of +0.0 (also when d_wte == NULL);
+ *   position term  wpe[pos] if 0 <= pos < n_pos, else a row of +0.0 (also when d_wpe == NULL); pos is d_pos[p] or the default
+ *                  (i, or p - cu[s] in a packed batch) -- default positions with T > n_pos are out of range from i = n_pos on;
+ *   f-gram term    unchanged by either: the id list of the raw tokens.  A negative token matches nothing; a token >= vocab
+ *                  still matches every f-gram that contains it (the index knows nothing of wte);
+ *   out[p,:]       cast((token term + f-gram term) + position term) in fp32, rounded once, like every other row.  On a
+ *                  SCONE_MODE_LONGEST_SUFFIX handle a matched f-gram replaces the token term, in or out of range;
+ *   status         bit 0 (SCONE_ST_BAD_TOKEN) is raised if and only if some position OF THE CALL has an id out of range for a
+ *                  table that was given (d_wte / d_wpe != NULL) -- in longest_suffix mode too, matched or not.  No other bit.
+ * Every other row of the output is what it is without the bad id, and nothing outside the output rows is written.  The rule
+ * holds for every lookup entry point below (scone_embed_varlen, scone_embed_base*, scone_embed_select, scone_finalize,
+ * scone_shard_gather_embed*, scone_shard_cols_embed) and for every launch on a part of a batch (staged chunks, the packed
+ * traversal, a sequence or token range): only the ids of the positions a call covers can raise the bit. */
 int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, const void *d_wte,
                 int64_t vocab, const void *d_wpe, int64_t n_pos, const int32_t *d_pos,
                 int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream);
@@ -261,7 +276,8 @@ int scone_embed(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, con
  * SCONE_EINVAL (scone_last_error names the reason): negative n_seqs / total_tokens, a null d_tok / d_cu_seqlens / d_out,
  * total_tokens > 2^31 - 1, a bad reduce / out_dtype, d % 8 != 0, a pinned-host table created with stage_tokens > 0 (its
  * staging pipeline chunks whole rectangular sequences; tables read in place from pinned host memory work).  The CONTENTS of d_cu_seqlens are the caller's contract and are not validated on the device;
- * whatever they are, no token outside d_tok[0, total_tokens) is read and nothing outside the total_tokens output rows written. */
+ * whatever they are, no token outside d_tok[0, total_tokens) is read and nothing outside the total_tokens output rows written.
+ * Token / position ids out of range: as scone_embed ("Ids out of range"), the default position being p - cu[s]. */
 int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
                        int64_t total_tokens, const void *d_wte, int64_t vocab, const void *d_wpe, int64_t n_pos,
                        const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream);
@@ -274,7 +290,8 @@ int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_c
  * == NULL (term omitted), d_pos == NULL (default positions) and the row_begin / row_end ownership rule (owned rows only,
  * divisor = full K) are scone_embed's; on a SCONE_MODE_LONGEST_SUFFIX handle a matched f-gram REPLACES the base row, as it
  * replaces the wte row there.  Token ids serve the match only: there is no vocabulary bound, a negative token matches nothing,
- * and SCONE_ST_BAD_TOKEN is raised only for a position id outside [0, n_pos).  Same launches, workspaces and stream ordering
+ * and SCONE_ST_BAD_TOKEN is raised only for a position id outside [0, n_pos) (its term is a row of +0.0: "Ids out of
+ * range" at scone_embed, without the token rule).  Same launches, workspaces and stream ordering
  * as scone_embed / scone_embed_varlen (no hidden synchronisation but the staged first-bind exception above); every road of
  * scone_embed takes a dense base (one launch, two kernels, any d % 8 == 0, the lane-group fallback for other dims, staged and
  * in-place pinned-host tables, the CU reserve).
@@ -350,7 +367,8 @@ int scone_embed_partial(scone_handle *h, const int32_t *d_tok, int32_t B, int32_
                         float *d_partial, int32_t *d_counts, scone_stream_t stream);
 /* out[t,:] = cast( (wte[tok[t]] + sum[t,:] / K_t) + wpe[pos[t]] ) for t in
  * [tok_begin, tok_end) of the flattened B*T positions; d_sum / d_counts / d_out
- * are indexed from tok_begin (slice-local), d_tok / d_pos are the full [B,T]. */
+ * are indexed from tok_begin (slice-local), d_tok / d_pos are the full [B,T].
+ * Token / position ids out of range: as scone_embed ("Ids out of range"); only the ids of [tok_begin, tok_end) are looked at. */
 int scone_finalize(scone_handle *h, const float *d_sum, const int32_t *d_counts,
                    const int32_t *d_tok, int32_t B, int32_t T, int64_t tok_begin, int64_t tok_end,
                    const void *d_wte, int64_t vocab, const void *d_wpe, int64_t n_pos,
@@ -451,6 +469,8 @@ int scone_shard_gather_add_records(scone_handle *h, const void *d_records_base, 
  * they reference must have been added): a loop that receives on one stream and reduces on another does this where the
  * records arrive, so that scone_shard_gather_embed_range finds the lists done and only launches the lookup. */
 int scone_shard_gather_remap_range(scone_handle *h, int32_t seq_begin, int32_t seq_end, scone_stream_t stream);
+/* (Token / position ids out of range: as scone_embed, "Ids out of range"; only the ids of sequences [seq_begin, seq_end) are
+ * looked at -- here and in scone_shard_gather_embed / scone_shard_cols_embed.) */
 int scone_shard_gather_embed_range(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, int32_t seq_begin,
                                    int32_t seq_end, const void *d_records_base, uint64_t n_total, const void *d_wte,
                                    int64_t vocab, const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce,
@@ -546,7 +566,8 @@ int scone_ipc_push(scone_handle *h, void *d_dst, const void *d_src, uint64_t byt
  * neither: the term is omitted.  d_out == d_base is the defined in-place call, any other overlap of the two [n_sel, d] ranges
  * returns SCONE_EINVAL.  d_sel may be unsorted and may repeat positions: each j is written on its own.  For d_sel[j] outside
  * [0, total_tokens) nothing is read, row j is NOT written and SCONE_ST_BAD_TOKEN is raised.  Whatever d_cu_seqlens holds, no
- * token outside d_tok[0, total_tokens) is read.
+ * token outside d_tok[0, total_tokens) is read.  Token / position ids out of range: as scone_embed ("Ids out of range"), for the
+ * token tok[d_sel[j]] and the position id of OUTPUT j; a bad id at a position that is not selected raises nothing.
  * n_sel comes from the host: ONE launch of ceil(n_sel / 4) workgroups for every n_sel that fits a grid, at every d % 8 == 0
  * and every table format (d = 768 / 1024 / 1280 specialised, any other dim -- and INT4 / MXFP4 at 768 / 1280 -- walked in
  * units of 8 elements); no workspace, no lock, no synchronisation; thread-safe like scone_embed.  n_sel == 0 or
