@@ -179,6 +179,59 @@ int scone_fit(int32_t device, const int32_t *d_tokens, int64_t n_tokens, const i
               uint32_t *d_keys_out, uint8_t *d_lens_out, uint32_t *d_counts_out, uint64_t out_cap,
               uint64_t *h_n_out, uint64_t *h_n_distinct, scone_stream_t stream);
 
+/* The same fit as a counter that is fed in chunks (what Counter.update gives the reference's fit loop, n_gram_extractor.py:72-104,
+ * with extract_all_n_grams :59-70 fixing the insertion order): a persistent state on the device that grows with the DISTINCT
+ * n-grams seen, can be finalised any number of times, exported and merged.  For every chunking, growth history, shard order and
+ * merge order the f-gram list equals scone_fit's on the whole corpus: same keys, same ids, same counts.  The state is an
+ * exact-key table (the packing and hash of the lookup index) with a 64-bit count and a 64-bit first sequence number per slot,
+ * 32 B per slot; counts never wrap.  No handle and no error string: return codes only, as scone_fit.  Every call selects the
+ * state's device and restores the caller's.  One state is used by one host thread at a time; states are independent.
+ * scone_fit_create: max_n in 1..4; initial_slots = 0 means 1024, any other value is rounded up to a power of two >= 1024.
+ * SCONE_EINVAL for a bad max_n / device or a null out, before any device work.  scone_fit_destroy(NULL) is a no-op. */
+typedef struct scone_fit_state scone_fit_state;
+int scone_fit_create(int32_t device, int32_t max_n, uint64_t initial_slots, scone_fit_state **out);
+void scone_fit_destroy(scone_fit_state *st);
+/* Counts one chunk of WHOLE texts (a text never spans two calls); layout as scone_fit: d_tokens[n_tokens] int32 back to back,
+ * d_text_offsets[n_texts + 1] int64 starting at 0.  Occurrences are numbered as scone_fit numbers them (texts in order; inside a
+ * text all 1-grams left to right, then all 2-grams, ...; extract_all_n_grams :59-70), starting at seq_base for the chunk's first
+ * text.  seq_base = UINT64_MAX continues where the previous chunk ended (next_seq); any other value is the caller's global number
+ * of this chunk's first occurrence, so that shards may be counted out of order or on other devices.  Afterwards
+ * next_seq = max(next_seq, seq_base + occurrences of the chunk).  n_texts = 0 or n_tokens = 0 is a no-op.
+ * The chunk is validated by a pass of its own BEFORE anything is counted, and a refused call leaves the state exactly as it
+ * was: SCONE_ERANGE for a negative token or one the key packing cannot hold (max_n = 4: >= 2^24 - 1); SCONE_EINVAL for offsets
+ * that do not start at 0, decrease, or do not end at n_tokens, for a null state, and for null arrays with non-zero sizes.
+ * Growth comes before the count, never inside it: with need = n_distinct + occurrences of the chunk, a table of fewer than
+ * 2 * need slots is moved to the smallest power of two >= 2 * need (old and new arrays coexist during the move; a failed
+ * allocation returns SCONE_ENOMEM with the old table intact), so slots < 4 * max(512, need) at every moment.
+ * Synchronises the stream (twice: it reads the validation status and the chunk's occurrence count, then the distinct counter). */
+int scone_fit_update(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens, const int64_t *d_text_offsets,
+                     int64_t n_texts, uint64_t seq_base, scone_stream_t stream);
+/* Host mirrors, exact after every call (none is left in flight): distinct n-grams held, occurrences counted by scone_fit_update
+ * (merged counts are not added), slots of the table (x 32 B = its device memory), growth events, next_seq.  Any output may be
+ * NULL.  No device work. */
+int scone_fit_stats(scone_fit_state *st, uint64_t *n_distinct, uint64_t *n_occurrences, uint64_t *slots, uint64_t *n_grows,
+                    uint64_t *next_seq);
+/* The f-gram list of everything counted so far, in scone_fit's order (count descending, ties by first sequence number ascending =
+ * Counter.most_common, n_gram_extractor.py:91-99): entries with count >= min_freq (and >= 1), two stable radix sorts, the count key
+ * 64 bits wide.  Row r of d_keys_out[*, max_n] / d_lens_out[*] / d_counts_out[*] (uint64, optional) is f-gram id r;
+ * *h_n_out = min(eligible, max_f_grams, out_cap) rows are written.  Does NOT consume the state: call it again with other
+ * min_freq / max_f_grams, or go on updating.  Scratch is sized by the eligible entries (48 B each + the sorts' workspace).
+ * Synchronises the stream. */
+int scone_fit_finalize(scone_fit_state *st, uint32_t min_freq, uint64_t max_f_grams, uint32_t *d_keys_out, uint8_t *d_lens_out,
+                       uint64_t *d_counts_out, uint64_t out_cap, uint64_t *h_n_out, scone_stream_t stream);
+/* Export: every distinct entry as d_keys_out[*, max_n] / d_lens_out / d_counts_out (64-bit) / d_first_out (first sequence number),
+ * in no particular order; *h_n_out = n_distinct.  out_cap < n_distinct returns SCONE_ERANGE with the needed number in *h_n_out
+ * and writes nothing.  Merge: adds n such entries to a state, count += d_counts[i], first = min(first, d_first[i]); the same key
+ * may occur more than once.  All entries are validated before any is applied: a length outside 1..max_n returns SCONE_EINVAL, a
+ * token the key packing cannot hold SCONE_ERANGE, and the state is unchanged.  Merge grows like an update, with
+ * need = n_distinct + n, and leaves next_seq alone (the caller passes an explicit seq_base to later updates).  Shards counted
+ * separately with explicit seq_base and merged in any order give the state that counting the corpus in order gives; export +
+ * merge is also checkpoint and resume.  Both synchronise the stream. */
+int scone_fit_export(scone_fit_state *st, uint32_t *d_keys_out, uint8_t *d_lens_out, uint64_t *d_counts_out,
+                     uint64_t *d_first_out, uint64_t out_cap, uint64_t *h_n_out, scone_stream_t stream);
+int scone_fit_merge(scone_fit_state *st, const uint32_t *d_keys, const uint8_t *d_lens, const uint64_t *d_counts,
+                    const uint64_t *d_first, uint64_t n, scone_stream_t stream);
+
 /* ---- table: rows (replaces EmbeddingCache.cache_embeddings storage,
  *      embedding_cache.py:56-111) ------------------------------------------- */
 /* Raw rows already in the handle's format.  rows: nrows * payload bytes

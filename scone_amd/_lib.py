@@ -66,6 +66,13 @@ SIGNATURES = {
     "scone_index_import": (C.c_int, [_P, _P, _P, _P, _U64]),
     "scone_fit": (C.c_int, [_I32, _P, _I64, _P, _I64, _I32, _U32, _U64, _P, _P, _P, _U64, C.POINTER(_U64),
                             C.POINTER(_U64), _P]),
+    "scone_fit_create": (C.c_int, [_I32, _I32, _U64, C.POINTER(_P)]),
+    "scone_fit_destroy": (None, [_P]),
+    "scone_fit_update": (C.c_int, [_P, _P, _I64, _P, _I64, _U64, _P]),
+    "scone_fit_stats": (C.c_int, [_P, C.POINTER(_U64), C.POINTER(_U64), C.POINTER(_U64), C.POINTER(_U64), C.POINTER(_U64)]),
+    "scone_fit_finalize": (C.c_int, [_P, _U32, _U64, _P, _P, _P, _U64, C.POINTER(_U64), _P]),
+    "scone_fit_export": (C.c_int, [_P, _P, _P, _P, _P, _U64, C.POINTER(_U64), _P]),
+    "scone_fit_merge": (C.c_int, [_P, _P, _P, _P, _P, _U64, _P]),
     "scone_table_upload": (C.c_int, [_P, _P, _P, _U64, _U64, C.c_int, _P]),
     "scone_table_download": (C.c_int, [_P, _P, _P, _U64, _U64, C.c_int, _P]),
     "scone_table_store_f32": (C.c_int, [_P, _P, _U64, _U64, _P]),

@@ -127,6 +127,158 @@ def fit_gpu(tokens: torch.Tensor, text_offsets: torch.Tensor, max_n: int, min_fr
             n_distinct.value)
 
 
+def fit_occurrences(text_lengths, max_n: int) -> int:
+    """n-gram occurrences of a run of texts of these lengths: ``sum_L sum_{n=1..min(max_n, L)} (L - n + 1)``, the number of
+    insertions the reference's ``Counter.update(extract_all_n_grams(text))`` makes (n_gram_extractor.py:59-70).  The
+    ``seq_base`` of a shard is this sum over all texts in front of it.  Runs without a GPU."""
+    lens = np.asarray(text_lengths, dtype=np.int64).reshape(-1)
+    total = 0
+    for n in range(1, int(max_n) + 1):
+        total += int(np.clip(lens - n + 1, 0, None).sum())
+    return total
+
+
+_SEQ_CONTINUE = 2**64 - 1   # scone_fit_update: seq_base = UINT64_MAX continues at next_seq
+
+
+class FitState:
+    """``scone_fit_state``: a device-resident n-gram counter that is fed in chunks of whole texts, grows with the distinct
+    n-grams seen, and can be finalised any number of times, exported and merged (include/scone_hip.h, "vocabulary
+    construction").  A context manager; ``close()`` frees the device memory.  Raises like :func:`fit_gpu`'s callers
+    expect: ``ValueError`` for ``SCONE_ERANGE`` (a token out of range) and ``SCONE_EINVAL``, ``RuntimeError`` otherwise."""
+
+    def __init__(self, max_n: int, device: Optional[torch.device] = None, initial_slots: int = 0) -> None:
+        self._st = None
+        lib = L.lib()
+        dev = torch.device(device) if device is not None else require_gpu()
+        require_gpu()
+        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self.max_n = int(max_n)
+        st = C.c_void_p()
+        self._check(lib.scone_fit_create(self.device.index, self.max_n, int(initial_slots), C.byref(st)), "scone_fit_create")
+        self._st = st
+
+    @staticmethod
+    def _check(rc: int, who: str) -> None:
+        if rc == L.OK:
+            return
+        text = f"{who} failed [{L.lib().scone_strerror(rc).decode()}]"
+        if rc == L.ERANGE:
+            raise ValueError(text + ": negative or too large token ids, or an output buffer too small")
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(text)
+        raise SconeError(text)
+
+    def close(self) -> None:
+        if self._st is not None:
+            L.lib().scone_fit_destroy(self._st)
+            self._st = None
+
+    def __enter__(self) -> "FitState":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if self._st is None:
+            raise SconeError("FitState is closed")
+        return self._st
+
+    def _dev(self, a, dtype: torch.dtype, what: str) -> torch.Tensor:
+        t = torch.as_tensor(a)
+        if t.dtype != dtype:
+            if t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f"FitState: {what} must hold integers")
+            if dtype == torch.int32 and t.numel() and (int(t.min()) < 0 or int(t.max()) > 2**31 - 2):
+                raise ValueError("FitState: token ids must be in [0, 2**31 - 2]")
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def update(self, tokens, text_offsets, seq_base: Optional[int] = None) -> None:
+        """Count one chunk of whole texts: ``tokens`` flat, ``text_offsets[n_texts + 1]`` from 0 to ``len(tokens)``.
+        ``seq_base=None`` numbers the chunk's occurrences after the previous chunk's; an integer is the global number of
+        its first occurrence (see :func:`fit_occurrences`).  A refused chunk (``ValueError``) changes nothing.  int32
+        tokens go to the device unchecked (the kernel validates them); wider integers are range-checked here."""
+        tok = self._dev(tokens, torch.int32, "tokens").reshape(-1)
+        off = self._dev(text_offsets, torch.int64, "text_offsets").reshape(-1)
+        n_texts = off.numel() - 1
+        if n_texts < 0:
+            raise ValueError("FitState.update: text_offsets must hold n_texts + 1 offsets")
+        base = _SEQ_CONTINUE if seq_base is None else int(seq_base)
+        if not 0 <= base <= _SEQ_CONTINUE:
+            raise ValueError("FitState.update: seq_base must fit 64 unsigned bits")
+        with torch.cuda.device(self.device):
+            rc = L.lib().scone_fit_update(self._handle(), _ptr(tok), tok.numel(), _ptr(off), n_texts, base, _stream())
+        self._check(rc, "scone_fit_update")
+
+    def stats(self) -> dict:
+        """``n_distinct``, ``n_occurrences`` (counted by ``update``), ``slots`` (x 32 B of device memory), ``n_grows``,
+        ``next_seq``."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._check(L.lib().scone_fit_stats(self._handle(), *[C.byref(x) for x in v]), "scone_fit_stats")
+        return dict(zip(("n_distinct", "n_occurrences", "slots", "n_grows", "next_seq"), (x.value for x in v)))
+
+    def finalize(self, min_freq: int, max_f_grams: int, out_cap: Optional[int] = None):
+        """The f-gram list of everything counted so far: ``(keys [S, max_n] uint32, lens [S] uint8, counts [S] uint64,
+        n_distinct)`` as numpy arrays, row r = f-gram id r (``Counter.most_common`` order).  Does not consume the state."""
+        n_distinct = self.stats()["n_distinct"]
+        cap = int(min(max(int(max_f_grams), 0), n_distinct))
+        if out_cap is not None:
+            cap = min(cap, int(out_cap))
+        keys = torch.zeros((max(cap, 1), self.max_n), dtype=torch.int32, device=self.device)
+        lens = torch.zeros(max(cap, 1), dtype=torch.uint8, device=self.device)
+        counts = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.device)
+        n_out = C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            rc = L.lib().scone_fit_finalize(self._handle(), int(min(max(int(min_freq), 0), 2**32 - 1)),
+                                            int(min(max(int(max_f_grams), 0), 2**64 - 1)), _ptr(keys), _ptr(lens), _ptr(counts),
+                                            cap, C.byref(n_out), _stream())
+        self._check(rc, "scone_fit_finalize")
+        n = n_out.value
+        return (keys[:n].cpu().numpy().view(np.uint32), lens[:n].cpu().numpy(), counts[:n].cpu().numpy().view(np.uint64),
+                n_distinct)
+
+    def export(self):
+        """Every distinct entry, in no particular order: ``(keys [D, max_n] uint32, lens [D] uint8, counts [D] uint64,
+        first [D] uint64)`` as numpy arrays -- what :meth:`merge` takes (shards, checkpoints)."""
+        cap = self.stats()["n_distinct"]
+        keys = torch.zeros((max(cap, 1), self.max_n), dtype=torch.int32, device=self.device)
+        lens = torch.zeros(max(cap, 1), dtype=torch.uint8, device=self.device)
+        counts = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.device)
+        first = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.device)
+        n_out = C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            rc = L.lib().scone_fit_export(self._handle(), _ptr(keys), _ptr(lens), _ptr(counts), _ptr(first), cap,
+                                          C.byref(n_out), _stream())
+        self._check(rc, "scone_fit_export")
+        n = n_out.value
+        return (keys[:n].cpu().numpy().view(np.uint32), lens[:n].cpu().numpy(), counts[:n].cpu().numpy().view(np.uint64),
+                first[:n].cpu().numpy().view(np.uint64))
+
+    def merge(self, keys, lens, counts, first) -> None:
+        """Add exported entries: ``count += counts[i]``, ``first = min(first, first[i])``.  ``next_seq`` is not touched."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        n = int(np.asarray(lens).shape[0])
+        if k.shape != (n, self.max_n):
+            raise ValueError("FitState.merge: keys must be [n, max_n]")
+        arrs = [torch.from_numpy(k.view(np.int32)),
+                torch.from_numpy(np.ascontiguousarray(lens, dtype=np.uint8)),
+                torch.from_numpy(np.ascontiguousarray(counts, dtype=np.uint64).view(np.int64)),
+                torch.from_numpy(np.ascontiguousarray(first, dtype=np.uint64).view(np.int64))]
+        if arrs[2].numel() != n or arrs[3].numel() != n:
+            raise ValueError("FitState.merge: lens, counts and first must have one entry per key")
+        d = [a.to(self.device).contiguous() for a in arrs]
+        with torch.cuda.device(self.device):
+            rc = L.lib().scone_fit_merge(self._handle(), _ptr(d[0]), _ptr(d[1]), _ptr(d[2]), _ptr(d[3]), n, _stream())
+        self._check(rc, "scone_fit_merge")
+
+
 class SconeTable:
     """Device-resident f-gram index (+ optional table shard)."""
 

@@ -110,10 +110,19 @@ class NGramExtractor:
             print(f"Extracted {len(self.f_grams)} f-grams")
         return self
 
-    def fit_gpu(self, tokenized_texts: Iterable[Sequence[int]], verbose: bool = True, device=None) -> "NGramExtractor":
+    def fit_gpu(self, tokenized_texts: Iterable[Sequence[int]], verbose: bool = True, device=None,
+                chunk_tokens: Optional[int] = None) -> "NGramExtractor":
         """Same result as :meth:`fit` (identical f-grams and ids), computed on the GPU by ``scone_fit``:
         hash-table counting of every n-gram + two stable radix sorts (count descending, first-seen
-        ascending).  Needs a GPU; the vocabulary stays in array form (see :meth:`from_arrays`)."""
+        ascending).  Needs a GPU; the vocabulary stays in array form (see :meth:`from_arrays`).
+
+        ``chunk_tokens=None``: one call over the whole corpus, which is materialised on the host and on the device.
+        An integer streams instead (``scone_fit_update``): the iterable is consumed lazily, texts are gathered until the
+        pending chunk holds at least ``chunk_tokens`` tokens (a longer single text is a chunk by itself), the chunk is
+        counted and dropped before more texts are pulled -- never more than one chunk's texts are alive on the host,
+        and device memory follows the distinct n-grams.  Same f-grams and ids; ``counts`` is ``uint64`` on this route."""
+        if chunk_tokens is not None:
+            return self._fit_gpu_stream(tokenized_texts, int(chunk_tokens), verbose, device)
         import torch
         from scone_amd.hip_backend import fit_gpu
         texts = [np.asarray(t, dtype=np.int64) for t in tokenized_texts]
@@ -132,6 +141,66 @@ class NGramExtractor:
         if verbose:
             print(f"Extracted {len(self)} f-grams")
         return self
+
+    @staticmethod
+    def _chunks(tokenized_texts: Iterable[Sequence[int]], chunk_tokens: int):
+        """Lazy chunk planner of the streaming fit: yields ``(tokens int32 [n], offsets int64 [texts + 1])`` of whole texts,
+        each chunk closed by the text that brings it to ``chunk_tokens`` tokens; empty texts keep their offset.  Raises
+        ``ValueError`` for a token outside ``[0, 2**31 - 2]`` when the chunk is closed, before it is yielded."""
+        if chunk_tokens < 1:
+            raise ValueError("chunk_tokens must be at least 1")
+
+        def close(texts, n_tok):
+            offsets = np.zeros(len(texts) + 1, dtype=np.int64)
+            np.cumsum([len(t) for t in texts], out=offsets[1:])
+            flat = np.concatenate(texts) if n_tok else np.zeros(0, dtype=np.int64)
+            if flat.size and (flat.min() < 0 or flat.max() > 2**31 - 2):
+                raise ValueError("fit_gpu: token ids must be in [0, 2**31 - 2]")
+            return flat.astype(np.int32), offsets
+
+        pending, n_tok = [], 0
+        for t in tokenized_texts:
+            pending.append(np.asarray(t, dtype=np.int64).reshape(-1))
+            n_tok += pending[-1].size
+            if n_tok >= chunk_tokens:
+                chunk = close(pending, n_tok)
+                pending, n_tok = [], 0
+                yield chunk
+                del chunk
+        if pending:
+            yield close(pending, n_tok)
+
+    def _fit_gpu_stream(self, tokenized_texts, chunk_tokens: int, verbose: bool, device) -> "NGramExtractor":
+        from scone_amd import hip_backend
+        with hip_backend.FitState(self.max_n, device=device) as state:
+            for tokens, offsets in self._chunks(tokenized_texts, chunk_tokens):
+                state.update(tokens, offsets)
+                del tokens, offsets
+            self._set_from_finalize(state, self.min_freq, self.max_f_grams)
+        if verbose:
+            print(f"Extracted {len(self)} f-grams")
+        return self
+
+    def _set_from_finalize(self, state, min_freq: int, max_f_grams: int) -> None:
+        keys, klens, counts, _ = state.finalize(min_freq, max_f_grams)
+        self._keys, self._lens = np.ascontiguousarray(keys), np.ascontiguousarray(klens)
+        self._f_gram_to_id = self._id_to_f_gram = self._f_grams = None
+        self._index = None
+        self.counts = counts
+
+    def fit_state(self, device=None, initial_slots: int = 0):
+        """A :class:`scone_amd.hip_backend.FitState` (``scone_fit_state``) with this extractor's ``max_n``: feed it chunks of
+        whole texts with ``update``, count shards elsewhere and ``merge`` them, then :meth:`from_fit_state`."""
+        from scone_amd import hip_backend
+        return hip_backend.FitState(self.max_n, device=device, initial_slots=initial_slots)
+
+    @classmethod
+    def from_fit_state(cls, state, min_freq: int, max_f_grams: int) -> "NGramExtractor":
+        """The extractor of one finalise of ``state`` (which is not consumed: sweeping ``min_freq`` / ``max_f_grams`` needs
+        no recount).  Array form, ``counts`` uint64, as ``fit_gpu(chunk_tokens=...)`` leaves it."""
+        ex = cls(max_n=state.max_n, min_freq=min_freq, max_f_grams=max_f_grams)
+        ex._set_from_finalize(state, min_freq, max_f_grams)
+        return ex
 
     def _set_from_list(self, grams: List[Tuple[int, ...]]) -> None:
         self._f_grams = set(grams)
