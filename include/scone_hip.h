@@ -100,7 +100,14 @@ typedef struct scone_cfg {
   int32_t max_n;           /* longest f-gram, 1..4 (NGramExtractor.max_n,
                               scone/tokenization/n_gram_extractor.py:39)                    */
   int32_t dim;             /* embedding_dim d (EmbeddingCache.embedding_dim, :45);
-                              multiple of 4 (F32), 8 (F16), 16 (I8), 128 (I4); 0 = index only */
+                              multiple of 4 (F32), 8 (F16), 16 (I8), 128 (I4); 0 = index only.
+                              There is no upper bound: rows of ANY width that the format's rule allows are
+                              supported on every road (quantiser, lookups, lists, row shards and their
+                              exchanges, pinned host memory read in place and through the cache of cold
+                              rows).  The widest the suite checks is d = 16384 (F32 and I4; I8, F16 and
+                              MXFP4 at 8192: tests/test_gpu_wide_rows.py).  Whatever the format,
+                              SCONE_MODE_LONGEST_SUFFIX, scone_embed_varlen, scone_embed_base_varlen and
+                              scone_embed_select need d % 8 == 0 (stated again at those calls)          */
   int32_t table_fmt;       /* SCONE_FMT_*                                                  */
   int32_t placement;       /* SCONE_PLACE_*                                                */
   uint64_t n_rows;         /* N = number of f-grams (global)                               */

@@ -201,9 +201,10 @@ __global__ __launch_bounds__(256) void k_stage_copy(const uint32_t *__restrict__
     const uint4 *src = reinterpret_cast<const uint4 *>(host.row(lr));
     uint4 *dst = reinterpret_cast<uint4 *>(cache_rows + (size_t)s * host.row_bytes);
     for (unsigned v = lane; v < host.row_bytes / 16; v += 64) dst[v] = src[v];
-    if (scale_bytes && lane < scale_bytes / 2)
-      reinterpret_cast<unsigned short *>(cache_scales + (size_t)(n_hot + s) * scale_bytes)[lane] =
-          reinterpret_cast<const unsigned short *>(scales + lr * scale_bytes)[lane];
+    // every scale byte of the row, 2 per lane per pass (MXFP4 at d = 8192 and INT4 at d = 16384 have 256: two passes)
+    for (unsigned b = lane; b < (unsigned)scale_bytes / 2; b += 64)
+      reinterpret_cast<unsigned short *>(cache_scales + (size_t)(n_hot + s) * scale_bytes)[b] =
+          reinterpret_cast<const unsigned short *>(scales + lr * scale_bytes)[b];
   }
 }
 

@@ -513,7 +513,9 @@ def test_row_exchange_between_three_shards_on_one_gpu(head):
 @pytest.mark.parametrize("stage_tokens", [0, 1024])
 def test_pinned_host_table(stage_tokens):
     """Rows >= 16 live in pinned host memory: read in place by the lookup kernel, or (stage_tokens > 0) through the HBM cache of
-    cold rows.  Both work by row bytes; the scales stay in HBM."""
+    cold rows.  Both work by row bytes.  Read in place, the scales are the table's own (always in HBM); the cache keeps its OWN
+    copy of a cold row's scales beside the row, filled by the kernel that copies the row (k_stage_copy) -- at d = 1024 that is 32
+    bytes per row; tests/test_gpu_wide_rows.py runs the widths at which a row has more than 128."""
     d, max_n = 1024, 3
     keys, lens = W._vocabulary(max_n)
     table, payload, scales, stored, wte, wpe = _tables(d, max_n)
