@@ -213,8 +213,9 @@ void scone_fit_destroy(scone_fit_state *st);
  * Synchronises the stream (twice: it reads the validation status and the chunk's occurrence count, then the distinct counter). */
 int scone_fit_update(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens, const int64_t *d_text_offsets,
                      int64_t n_texts, uint64_t seq_base, scone_stream_t stream);
-/* Host mirrors, exact after every call (none is left in flight): distinct n-grams held, occurrences counted by scone_fit_update
- * (merged counts are not added), slots of the table (x 32 B = its device memory), growth events, next_seq.  Any output may be
+/* Host mirrors, exact after every call (none is left in flight): distinct n-grams held, occurrences FED to scone_fit_update /
+ * scone_fit_update_part (every occurrence of every accepted chunk, whether its key was in the call's partition or not; merged
+ * counts are not added), slots of the table (x 32 B = its device memory), growth events, next_seq.  Any output may be
  * NULL.  No device work. */
 int scone_fit_stats(scone_fit_state *st, uint64_t *n_distinct, uint64_t *n_occurrences, uint64_t *slots, uint64_t *n_grows,
                     uint64_t *next_seq);
@@ -238,6 +239,52 @@ int scone_fit_export(scone_fit_state *st, uint32_t *d_keys_out, uint8_t *d_lens_
                      uint64_t *d_first_out, uint64_t out_cap, uint64_t *h_n_out, scone_stream_t stream);
 int scone_fit_merge(scone_fit_state *st, const uint32_t *d_keys, const uint8_t *d_lens, const uint64_t *d_counts,
                     const uint64_t *d_first, uint64_t n, scone_stream_t stream);
+
+/* Exact fit beyond one device's memory: key-hash partitions.  The key space is cut into n_parts parts by a hash of the key, and
+ * a pass over the corpus counts the keys of ONE part; the state then holds about 1 / n_parts of the distinct n-grams, at the
+ * price of n_parts passes (or n_parts devices, one part each, nothing exchanged).
+ *
+ * The partition function is a contract -- selections written by one process are routed by another.  With
+ * (lo, ext) = scone_pack_key(tokens, len, max_n), the packed key of the index (tokens stored + 1; max_n <= 3: 32 bits per
+ * token, lo = t0 | t1 << 32, ext = t2; max_n = 4: 24 bits per token, lo = t0 | t1 << 24 | (t2 & 0xFFFF) << 48,
+ * ext = t2 >> 16 | t3 << 8), and scone_hash_key(lo, ext) the index's 64-bit hash (x = lo ^ ext * 0x9E3779B97F4A7C15;
+ * x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31):
+ *
+ *     part = (uint32_t)(((scone_hash_key(lo, ext) >> 32) * (uint64_t)n_parts) >> 32)
+ *
+ * It is taken from the UPPER 32 bits of the hash on purpose: the table picks a key's home slot from the LOWER bits,
+ * hash & (slots - 1).  A partition taken from the lower bits would put a part's keys on 1 / n_parts of the home slots and
+ * turn probing into long clusters.
+ *
+ * Why it is exact: every key lives in exactly one part, so its count and its first sequence number are complete inside that
+ * part.  A key among the global top max_f_grams (count descending, first number ascending) has fewer than max_f_grams keys in
+ * front of it globally, hence fewer in its own part: it is in its part's top max_f_grams.  So each part is finalised on its
+ * own (scone_fit_finalize_seq), and merging the selections of all parts into a fresh state (scone_fit_merge) and finalising
+ * that gives scone_fit's list: same keys, same ids, same counts.
+ *
+ * scone_fit_partition: pure host, no device work.  h_keys[n, max_n] / h_lens[n] as scone_index_build takes them;
+ * h_part_out[n] receives each key's part.  SCONE_EINVAL: max_n outside 1..4, n_parts == 0, a length outside 1..max_n, null
+ * arrays with n > 0.  SCONE_ERANGE: a token the key packing cannot hold (max_n = 4: >= 2^24 - 1).  On a refusal nothing is
+ * written. */
+int scone_fit_partition(const uint32_t *h_keys, const uint8_t *h_lens, uint64_t n, int32_t max_n, uint32_t n_parts,
+                        uint32_t *h_part_out);
+/* scone_fit_update in every respect but one: only occurrences whose key has partition `part` of `n_parts` are counted; a key
+ * of another part never takes a slot.  Unchanged: the validation pass comes first and a refused call leaves the state as it
+ * was; growth comes before the count with need = n_distinct + ALL occurrences of the chunk (an upper bound, so no growth
+ * inside a count and every probe loop ends); EVERY occurrence of the chunk is numbered whether it is counted or not, and
+ * next_seq and n_occurrences advance by all of them, so every part of one corpus ends at the same next_seq.
+ * part >= n_parts or n_parts == 0 returns SCONE_EINVAL before any device work.  (part = 0, n_parts = 1) is scone_fit_update.
+ * The state does not remember partitions: it stays a function of the multiset of (key, sequence number) pairs it was fed, and
+ * feeding several parts to one state is legal (all n_parts parts of a chunk, each with the chunk's seq_base = scone_fit_update).
+ * Memory per part: slots < 4 * max(512, distinct keys of the part + occurrences of one chunk). */
+int scone_fit_update_part(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens, const int64_t *d_text_offsets,
+                          int64_t n_texts, uint64_t seq_base, uint32_t part, uint32_t n_parts, scone_stream_t stream);
+/* scone_fit_finalize's list, row for row, plus the first sequence number of every row in d_first_out[*] (uint64): what
+ * scone_fit_merge takes, so a part's selection is directly mergeable (scone_fit_export carries first numbers too, but of every
+ * distinct entry).  d_counts_out and d_first_out may each be NULL.  Does not consume the state.  Synchronises the stream. */
+int scone_fit_finalize_seq(scone_fit_state *st, uint32_t min_freq, uint64_t max_f_grams, uint32_t *d_keys_out, uint8_t *d_lens_out,
+                           uint64_t *d_counts_out, uint64_t *d_first_out, uint64_t out_cap, uint64_t *h_n_out,
+                           scone_stream_t stream);
 
 /* ---- table: rows (replaces EmbeddingCache.cache_embeddings storage,
  *      embedding_cache.py:56-111) ------------------------------------------- */

@@ -73,6 +73,9 @@ SIGNATURES = {
     "scone_fit_finalize": (C.c_int, [_P, _U32, _U64, _P, _P, _P, _U64, C.POINTER(_U64), _P]),
     "scone_fit_export": (C.c_int, [_P, _P, _P, _P, _P, _U64, C.POINTER(_U64), _P]),
     "scone_fit_merge": (C.c_int, [_P, _P, _P, _P, _P, _U64, _P]),
+    "scone_fit_partition": (C.c_int, [_P, _P, _U64, _I32, _U32, _P]),
+    "scone_fit_update_part": (C.c_int, [_P, _P, _I64, _P, _I64, _U64, _U32, _U32, _P]),
+    "scone_fit_finalize_seq": (C.c_int, [_P, _U32, _U64, _P, _P, _P, _P, _U64, C.POINTER(_U64), _P]),
     "scone_table_upload": (C.c_int, [_P, _P, _P, _U64, _U64, C.c_int, _P]),
     "scone_table_download": (C.c_int, [_P, _P, _P, _U64, _U64, C.c_int, _P]),
     "scone_table_store_f32": (C.c_int, [_P, _P, _U64, _U64, _P]),

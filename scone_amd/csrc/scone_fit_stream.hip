@@ -12,6 +12,10 @@
 // always ends and no key is ever dropped; the result is a function of the multiset of (key, sequence number) pairs fed
 // and not of chunking, growth history or order (count: a sum; first: a minimum).
 //
+// Key-hash partitions (scone_fit_update_part): the same call counting only the keys whose hash falls into one of n_parts parts.
+// A key lives in exactly one part, so its count and first number are complete there, and each part is finalised on its own
+// (scone_fit_finalize_seq gives rows that scone_fit_merge takes): device memory follows the distinct keys of ONE part.
+//
 // Half-written slots: a slot whose lo word is claimed and whose tag word is still 0 exists only INSIDE a count / merge /
 // rehash launch, where every reader goes through the CAS on the tag word.  Every launch that reads the table otherwise
 // (rehash source, export, finalise) runs after the writer's launch has completed on the stream, and tests the tag word.
@@ -74,11 +78,18 @@ __global__ __launch_bounds__(256) void k_fits_validate(const int32_t *__restrict
   }
 }
 
-// Find-or-claim the slot of (lo, tag).  Returns the slot; *claimed = this thread wrote the tag word.  The table always has
-// room (growth rule), so the loop ends; cap + 1 probes without success returns ~0 and the caller raises INDEX_FULL.
-__device__ inline unsigned long long fits_slot_of(scone_slot *slots, unsigned long long mask, unsigned long long lo,
-                                                  unsigned long long tag, uint32_t ext, bool *claimed) {
-  unsigned long long s = scone_hash_key(lo, ext) & mask;
+// The key-hash partition of scone_fit_partition / scone_fit_update_part (the formula is a contract, include/scone_hip.h): the
+// UPPER 32 bits of the hash scaled to [0, n_parts).  The home slot is hash & mask, the LOWER bits, so the keys of one part
+// still spread over the whole table; a partition taken from the lower bits would leave a part 1 / n_parts of the home slots.
+__host__ __device__ inline uint32_t fits_part_of(unsigned long long hash, uint32_t n_parts) {
+  return (uint32_t)(((hash >> 32) * (unsigned long long)n_parts) >> 32);
+}
+
+// Find-or-claim the slot of (lo, tag), probing from the home slot s.  Returns the slot; *claimed = this thread wrote the tag
+// word.  The table always has room (growth rule), so the loop ends; cap + 1 probes without success returns ~0 and the caller
+// raises INDEX_FULL.
+__device__ inline unsigned long long fits_slot_from(scone_slot *slots, unsigned long long mask, unsigned long long s,
+                                                    unsigned long long lo, unsigned long long tag, bool *claimed) {
   for (unsigned long long probe = 0; probe <= mask; ++probe) {
     const unsigned long long old = atomicCAS(&slots[s].lo, 0ull, lo);
     if (old == 0ull || old == lo) {
@@ -93,15 +104,25 @@ __device__ inline unsigned long long fits_slot_of(scone_slot *slots, unsigned lo
   return ~0ull;
 }
 
+__device__ inline unsigned long long fits_slot_of(scone_slot *slots, unsigned long long mask, unsigned long long lo,
+                                                  unsigned long long tag, uint32_t ext, bool *claimed) {
+  return fits_slot_from(slots, mask, scone_hash_key(lo, ext) & mask, lo, tag, claimed);
+}
+
 // One item per (flat token position g, n): count the n-gram starting at g if it fits in its text (k_fit_count with 64-bit
 // counts, a caller-given sequence base and the distinct counter).  The chunk has passed k_fits_validate.
+// PART: count only the keys of partition `part` of `n_parts` (scone_fit_update_part).  The key is hashed once; an
+// out-of-partition key leaves before the first CAS, so it never claims a slot or touches n_distinct, and the hash is reused for
+// the home slot.  Its occurrence still has its sequence number: numbering is by position, not by what is counted.  With PART
+// false the two trailing arguments are unused and the kernel is scone_fit_update's as it always was.
+template <bool PART>
 __global__ __launch_bounds__(256) void k_fits_count(scone_slot *__restrict__ slots, unsigned long long mask,
                                                     unsigned long long *__restrict__ cnt, unsigned long long *__restrict__ first,
                                                     const int32_t *__restrict__ tok, long long n_tokens,
                                                     const long long *__restrict__ offsets, long long n_texts,
                                                     const unsigned long long *__restrict__ base_seq, unsigned long long seq_base,
                                                     int max_n, unsigned long long *__restrict__ n_distinct,
-                                                    uint32_t *__restrict__ status) {
+                                                    uint32_t *__restrict__ status, uint32_t part, uint32_t n_parts) {
   const unsigned long long work = (unsigned long long)n_tokens * (unsigned long long)max_n;
   for (unsigned long long gid = grid_tid(); gid < work; gid += grid_size()) {
     const int n = (int)(gid / (unsigned long long)n_tokens) + 1;
@@ -119,12 +140,19 @@ __global__ __launch_bounds__(256) void k_fits_count(scone_slot *__restrict__ slo
     for (int j = 0; j < SCONE_MAX_N; ++j)
       if (j < n) k[j] = (uint32_t)tok[g + j];
     const scone_key key = scone_pack_key(k, n, max_n);
+    unsigned long long hash = 0ull;
+    if constexpr (PART) {
+      hash = scone_hash_key(key.lo, key.ext);
+      if (fits_part_of(hash, n_parts) != part) continue;
+    }
     // insertion order inside the text: all 1-grams, then all 2-grams, ...
     unsigned long long seq = seq_base + base_seq[lo] + (unsigned long long)i;
     for (int m = 1; m < n; ++m) seq += (unsigned long long)(L - m + 1);
     const unsigned long long tag = ((unsigned long long)key.ext << 32) | 1ull;
     bool claimed = false;
-    const unsigned long long s = fits_slot_of(slots, mask, key.lo, tag, key.ext, &claimed);
+    unsigned long long s;
+    if constexpr (PART) s = fits_slot_from(slots, mask, hash & mask, key.lo, tag, &claimed);
+    else s = fits_slot_of(slots, mask, key.lo, tag, key.ext, &claimed);
     if (s == ~0ull) {
       atomicOr(status, SCONE_ST_INDEX_FULL);
       continue;
@@ -271,17 +299,22 @@ __global__ __launch_bounds__(256) void k_fits_gather_counts(const unsigned long 
   for (unsigned long long j = grid_tid(); j < m; j += grid_size()) out[j] = cnt[slot[j]];
 }
 
+// counts and firsts are optional outputs (firsts: scone_fit_finalize_seq; first[] is the state's per-slot array)
 __global__ __launch_bounds__(256) void k_fits_emit(const scone_slot *__restrict__ slots,
+                                                   const unsigned long long *__restrict__ first,
                                                    const unsigned long long *__restrict__ slot,
                                                    const unsigned long long *__restrict__ cnt_sorted, unsigned long long n_out,
                                                    int max_n, uint32_t *__restrict__ keys, uint8_t *__restrict__ lens,
-                                                   unsigned long long *__restrict__ counts) {
+                                                   unsigned long long *__restrict__ counts,
+                                                   unsigned long long *__restrict__ firsts) {
   for (unsigned long long r = grid_tid(); r < n_out; r += grid_size()) {
+    const unsigned long long s = slot[r];
     uint32_t v[SCONE_MAX_N];
-    const int len = fits_unpack(slots[slot[r]], max_n, v);
+    const int len = fits_unpack(slots[s], max_n, v);
     for (int j = 0; j < max_n; ++j) keys[r * max_n + j] = v[j];
     lens[r] = (uint8_t)len;
     if (counts) counts[r] = cnt_sorted[r];
+    if (firsts) firsts[r] = first[s];
   }
 }
 
@@ -416,8 +449,10 @@ extern "C" int scone_fit_stats(scone_fit_state *st, uint64_t *n_distinct, uint64
   return SCONE_OK;
 }
 
-extern "C" int scone_fit_update(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens, const int64_t *d_text_offsets,
-                                int64_t n_texts, uint64_t seq_base, scone_stream_t stream) {
+// scone_fit_update (n_parts = 1: the unfiltered kernel) and scone_fit_update_part (n_parts > 1: the filtering one).  Everything
+// but the count launch is shared: validation, numbering and growth look at ALL occurrences of the chunk.
+static int fits_update(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens, const int64_t *d_text_offsets,
+                       int64_t n_texts, uint64_t seq_base, uint32_t part, uint32_t n_parts, scone_stream_t stream) {
   if (!st || n_tokens < 0 || n_texts < 0) return SCONE_EINVAL;
   if (n_tokens == 0 || n_texts == 0) return SCONE_OK;
   if (!d_tokens || !d_text_offsets) return SCONE_EINVAL;
@@ -462,9 +497,14 @@ extern "C" int scone_fit_update(scone_fit_state *st, const int32_t *d_tokens, in
   // 3. count
   const unsigned long long seq0 = seq_base == UINT64_MAX ? st->next_seq : seq_base;
   const unsigned long long work = (unsigned long long)n_tokens * (unsigned long long)max_n;
-  hipLaunchKernelGGL(k_fits_count, dim3(blocks_for(work)), dim3(256), 0, s, st->slots, st->cap - 1, st->cnt, st->first, d_tokens,
-                     (long long)n_tokens, (const long long *)d_text_offsets, (long long)n_texts, base, seq0, max_n,
-                     st->d_counters, st->d_status);
+  if (n_parts > 1)
+    hipLaunchKernelGGL(k_fits_count<true>, dim3(blocks_for(work)), dim3(256), 0, s, st->slots, st->cap - 1, st->cnt, st->first,
+                       d_tokens, (long long)n_tokens, (const long long *)d_text_offsets, (long long)n_texts, base, seq0, max_n,
+                       st->d_counters, st->d_status, part, n_parts);
+  else
+    hipLaunchKernelGGL(k_fits_count<false>, dim3(blocks_for(work)), dim3(256), 0, s, st->slots, st->cap - 1, st->cnt, st->first,
+                       d_tokens, (long long)n_tokens, (const long long *)d_text_offsets, (long long)n_texts, base, seq0, max_n,
+                       st->d_counters, st->d_status, 0u, 1u);
   FIT_HIP(hipGetLastError());
   unsigned long long h_distinct = 0;
   FIT_HIP(hipMemcpyAsync(&h_distinct, st->d_counters, 8, hipMemcpyDeviceToHost, s));
@@ -477,9 +517,40 @@ extern "C" int scone_fit_update(scone_fit_state *st, const int32_t *d_tokens, in
   return SCONE_OK;
 }
 
-extern "C" int scone_fit_finalize(scone_fit_state *st, uint32_t min_freq, uint64_t max_f_grams, uint32_t *d_keys_out,
-                                  uint8_t *d_lens_out, uint64_t *d_counts_out, uint64_t out_cap, uint64_t *h_n_out,
-                                  scone_stream_t stream) {
+extern "C" int scone_fit_update(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens, const int64_t *d_text_offsets,
+                                int64_t n_texts, uint64_t seq_base, scone_stream_t stream) {
+  return fits_update(st, d_tokens, n_tokens, d_text_offsets, n_texts, seq_base, 0u, 1u, stream);
+}
+
+extern "C" int scone_fit_update_part(scone_fit_state *st, const int32_t *d_tokens, int64_t n_tokens,
+                                     const int64_t *d_text_offsets, int64_t n_texts, uint64_t seq_base, uint32_t part,
+                                     uint32_t n_parts, scone_stream_t stream) {
+  if (!st || n_parts == 0 || part >= n_parts) return SCONE_EINVAL;  // before any device work
+  return fits_update(st, d_tokens, n_tokens, d_text_offsets, n_texts, seq_base, part, n_parts, stream);
+}
+
+extern "C" int scone_fit_partition(const uint32_t *h_keys, const uint8_t *h_lens, uint64_t n, int32_t max_n, uint32_t n_parts,
+                                   uint32_t *h_part_out) {
+  if (max_n < 1 || max_n > SCONE_MAX_N || n_parts == 0) return SCONE_EINVAL;
+  if (n == 0) return SCONE_OK;
+  if (!h_keys || !h_lens || !h_part_out) return SCONE_EINVAL;
+  // two passes: a refusal writes nothing
+  for (int pass = 0; pass < 2; ++pass)
+    for (uint64_t i = 0; i < n; ++i) {
+      const int len = h_lens[i];
+      if (len < 1 || len > max_n) return SCONE_EINVAL;
+      uint32_t k[SCONE_MAX_N] = {0u, 0u, 0u, 0u};
+      for (int j = 0; j < len; ++j) k[j] = h_keys[i * (uint64_t)max_n + j];
+      const scone_key key = scone_pack_key(k, len, max_n);
+      if (!key.ok) return SCONE_ERANGE;
+      if (pass) h_part_out[i] = fits_part_of(scone_hash_key(key.lo, key.ext), n_parts);
+    }
+  return SCONE_OK;
+}
+
+static int fits_finalize(scone_fit_state *st, uint32_t min_freq, uint64_t max_f_grams, uint32_t *d_keys_out, uint8_t *d_lens_out,
+                         uint64_t *d_counts_out, uint64_t *d_first_out, uint64_t out_cap, uint64_t *h_n_out,
+                         scone_stream_t stream) {
   if (!st || !h_n_out) return SCONE_EINVAL;
   *h_n_out = 0;
   scone_device_guard dev_guard__(st->device);
@@ -530,12 +601,25 @@ extern "C" int scone_fit_finalize(scone_fit_state *st, uint32_t min_freq, uint64
 
   unsigned long long n_out = m < max_f_grams ? m : max_f_grams;
   if (n_out > out_cap) n_out = out_cap;
-  hipLaunchKernelGGL(k_fits_emit, dim3(blocks_for(n_out)), dim3(256), 0, s, st->slots, sel_slot.as<unsigned long long>(),
-                     c2.as<unsigned long long>(), n_out, st->max_n, d_keys_out, d_lens_out, (unsigned long long *)d_counts_out);
+  hipLaunchKernelGGL(k_fits_emit, dim3(blocks_for(n_out)), dim3(256), 0, s, st->slots, st->first, sel_slot.as<unsigned long long>(),
+                     c2.as<unsigned long long>(), n_out, st->max_n, d_keys_out, d_lens_out, (unsigned long long *)d_counts_out,
+                     (unsigned long long *)d_first_out);
   FIT_HIP(hipGetLastError());
   FIT_HIP(hipStreamSynchronize(s));
   *h_n_out = n_out;
   return SCONE_OK;
+}
+
+extern "C" int scone_fit_finalize(scone_fit_state *st, uint32_t min_freq, uint64_t max_f_grams, uint32_t *d_keys_out,
+                                  uint8_t *d_lens_out, uint64_t *d_counts_out, uint64_t out_cap, uint64_t *h_n_out,
+                                  scone_stream_t stream) {
+  return fits_finalize(st, min_freq, max_f_grams, d_keys_out, d_lens_out, d_counts_out, nullptr, out_cap, h_n_out, stream);
+}
+
+extern "C" int scone_fit_finalize_seq(scone_fit_state *st, uint32_t min_freq, uint64_t max_f_grams, uint32_t *d_keys_out,
+                                      uint8_t *d_lens_out, uint64_t *d_counts_out, uint64_t *d_first_out, uint64_t out_cap,
+                                      uint64_t *h_n_out, scone_stream_t stream) {
+  return fits_finalize(st, min_freq, max_f_grams, d_keys_out, d_lens_out, d_counts_out, d_first_out, out_cap, h_n_out, stream);
 }
 
 extern "C" int scone_fit_export(scone_fit_state *st, uint32_t *d_keys_out, uint8_t *d_lens_out, uint64_t *d_counts_out,

@@ -138,7 +138,25 @@ def fit_occurrences(text_lengths, max_n: int) -> int:
     return total
 
 
-_SEQ_CONTINUE = 2**64 - 1   # scone_fit_update: seq_base = UINT64_MAX continues at next_seq
+def fit_partition(keys, lens, max_n: int, n_parts: int) -> np.ndarray:
+    """``scone_fit_partition``: the key-hash partition ``uint32 [n]`` of ``keys [n, max_n]`` / ``lens [n]`` -- which part of
+    ``n_parts`` counts each key under ``FitState.update(..., part=, n_parts=)``.  Runs without a GPU.  ``ValueError`` for a
+    bad ``max_n`` / ``n_parts`` / length, ``IndexError`` for a token the key packing cannot hold."""
+    k = np.ascontiguousarray(keys, dtype=np.uint32)
+    l = np.ascontiguousarray(lens, dtype=np.uint8).reshape(-1)
+    if k.shape != (l.shape[0], int(max_n)):
+        raise ValueError("fit_partition: keys must be [n, max_n]")
+    if not 0 <= int(n_parts) < 2**32:
+        raise ValueError("fit_partition: n_parts must fit 32 unsigned bits")
+    out = np.zeros(l.shape[0], dtype=np.uint32)
+    rc = L.lib().scone_fit_partition(k.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p), l.shape[0], int(max_n),
+                                     int(n_parts), out.ctypes.data_as(C.c_void_p))
+    if rc != L.OK:
+        _raise(rc, "scone_fit_partition failed")
+    return out
+
+
+_SEQ_CONTINUE = 2**64 - 1  # scone_fit_update: seq_base = UINT64_MAX continues at next_seq
 
 
 class FitState:
@@ -200,11 +218,19 @@ class FitState:
                 raise ValueError("FitState: token ids must be in [0, 2**31 - 2]")
         return t.to(device=self.device, dtype=dtype).contiguous()
 
-    def update(self, tokens, text_offsets, seq_base: Optional[int] = None) -> None:
+    def update(self, tokens, text_offsets, seq_base: Optional[int] = None, part: Optional[int] = None,
+               n_parts: Optional[int] = None) -> None:
         """Count one chunk of whole texts: ``tokens`` flat, ``text_offsets[n_texts + 1]`` from 0 to ``len(tokens)``.
         ``seq_base=None`` numbers the chunk's occurrences after the previous chunk's; an integer is the global number of
         its first occurrence (see :func:`fit_occurrences`).  A refused chunk (``ValueError``) changes nothing.  int32
-        tokens go to the device unchecked (the kernel validates them); wider integers are range-checked here."""
+        tokens go to the device unchecked (the kernel validates them); wider integers are range-checked here.
+        ``part`` / ``n_parts`` (both or neither): count only the keys of that key-hash partition
+        (``scone_fit_update_part``, :func:`fit_partition`); every occurrence is still numbered and adds to
+        ``n_occurrences`` and ``next_seq``."""
+        if (part is None) != (n_parts is None):
+            raise ValueError("FitState.update: give both part and n_parts, or neither")
+        if part is not None and not (0 <= int(part) < 2**32 and 0 <= int(n_parts) < 2**32):
+            raise ValueError("FitState.update: part and n_parts must fit 32 unsigned bits")
         tok = self._dev(tokens, torch.int32, "tokens").reshape(-1)
         off = self._dev(text_offsets, torch.int64, "text_offsets").reshape(-1)
         n_texts = off.numel() - 1
@@ -214,8 +240,12 @@ class FitState:
         if not 0 <= base <= _SEQ_CONTINUE:
             raise ValueError("FitState.update: seq_base must fit 64 unsigned bits")
         with torch.cuda.device(self.device):
-            rc = L.lib().scone_fit_update(self._handle(), _ptr(tok), tok.numel(), _ptr(off), n_texts, base, _stream())
-        self._check(rc, "scone_fit_update")
+            if part is None:
+                rc = L.lib().scone_fit_update(self._handle(), _ptr(tok), tok.numel(), _ptr(off), n_texts, base, _stream())
+            else:
+                rc = L.lib().scone_fit_update_part(self._handle(), _ptr(tok), tok.numel(), _ptr(off), n_texts, base, int(part),
+                                                   int(n_parts), _stream())
+        self._check(rc, "scone_fit_update" if part is None else "scone_fit_update_part")
 
     def stats(self) -> dict:
         """``n_distinct``, ``n_occurrences`` (counted by ``update``), ``slots`` (x 32 B of device memory), ``n_grows``,
@@ -224,9 +254,11 @@ class FitState:
         self._check(L.lib().scone_fit_stats(self._handle(), *[C.byref(x) for x in v]), "scone_fit_stats")
         return dict(zip(("n_distinct", "n_occurrences", "slots", "n_grows", "next_seq"), (x.value for x in v)))
 
-    def finalize(self, min_freq: int, max_f_grams: int, out_cap: Optional[int] = None):
+    def finalize(self, min_freq: int, max_f_grams: int, out_cap: Optional[int] = None, with_first: bool = False):
         """The f-gram list of everything counted so far: ``(keys [S, max_n] uint32, lens [S] uint8, counts [S] uint64,
-        n_distinct)`` as numpy arrays, row r = f-gram id r (``Counter.most_common`` order).  Does not consume the state."""
+        n_distinct)`` as numpy arrays, row r = f-gram id r (``Counter.most_common`` order).  Does not consume the state.
+        ``with_first=True`` (``scone_fit_finalize_seq``) appends ``first [S] uint64``, every row's first sequence number:
+        ``(keys, lens, counts, n_distinct, first)``, whose arrays are what :meth:`merge` takes."""
         n_distinct = self.stats()["n_distinct"]
         cap = int(min(max(int(max_f_grams), 0), n_distinct))
         if out_cap is not None:
@@ -235,14 +267,21 @@ class FitState:
         lens = torch.zeros(max(cap, 1), dtype=torch.uint8, device=self.device)
         counts = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.device)
         n_out = C.c_uint64(0)
+        min_freq = int(min(max(int(min_freq), 0), 2**32 - 1))
+        max_f_grams = int(min(max(int(max_f_grams), 0), 2**64 - 1))
         with torch.cuda.device(self.device):
-            rc = L.lib().scone_fit_finalize(self._handle(), int(min(max(int(min_freq), 0), 2**32 - 1)),
-                                            int(min(max(int(max_f_grams), 0), 2**64 - 1)), _ptr(keys), _ptr(lens), _ptr(counts),
-                                            cap, C.byref(n_out), _stream())
-        self._check(rc, "scone_fit_finalize")
+            if with_first:
+                first = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.device)
+                rc = L.lib().scone_fit_finalize_seq(self._handle(), min_freq, max_f_grams, _ptr(keys), _ptr(lens), _ptr(counts),
+                                                    _ptr(first), cap, C.byref(n_out), _stream())
+            else:
+                rc = L.lib().scone_fit_finalize(self._handle(), min_freq, max_f_grams, _ptr(keys), _ptr(lens), _ptr(counts),
+                                                cap, C.byref(n_out), _stream())
+        self._check(rc, "scone_fit_finalize_seq" if with_first else "scone_fit_finalize")
         n = n_out.value
-        return (keys[:n].cpu().numpy().view(np.uint32), lens[:n].cpu().numpy(), counts[:n].cpu().numpy().view(np.uint64),
-                n_distinct)
+        res = (keys[:n].cpu().numpy().view(np.uint32), lens[:n].cpu().numpy(), counts[:n].cpu().numpy().view(np.uint64),
+               n_distinct)
+        return res + (first[:n].cpu().numpy().view(np.uint64),) if with_first else res
 
     def export(self):
         """Every distinct entry, in no particular order: ``(keys [D, max_n] uint32, lens [D] uint8, counts [D] uint64,

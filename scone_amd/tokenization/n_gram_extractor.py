@@ -111,7 +111,7 @@ class NGramExtractor:
         return self
 
     def fit_gpu(self, tokenized_texts: Iterable[Sequence[int]], verbose: bool = True, device=None,
-                chunk_tokens: Optional[int] = None) -> "NGramExtractor":
+                chunk_tokens: Optional[int] = None, partitions: Optional[int] = None) -> "NGramExtractor":
         """Same result as :meth:`fit` (identical f-grams and ids), computed on the GPU by ``scone_fit``:
         hash-table counting of every n-gram + two stable radix sorts (count descending, first-seen
         ascending).  Needs a GPU; the vocabulary stays in array form (see :meth:`from_arrays`).
@@ -120,7 +120,24 @@ class NGramExtractor:
         An integer streams instead (``scone_fit_update``): the iterable is consumed lazily, texts are gathered until the
         pending chunk holds at least ``chunk_tokens`` tokens (a longer single text is a chunk by itself), the chunk is
         counted and dropped before more texts are pulled -- never more than one chunk's texts are alive on the host,
-        and device memory follows the distinct n-grams.  Same f-grams and ids; ``counts`` is ``uint64`` on this route."""
+        and device memory follows the distinct n-grams.  Same f-grams and ids; ``counts`` is ``uint64`` on this route.
+
+        ``partitions=P`` (needs ``chunk_tokens``; ``None`` or 1 is the plain streaming route): the exact fit when even the
+        distinct n-grams do not fit the device.  The key space is cut into ``P`` parts by a hash of the key
+        (``scone_fit_partition``); pass ``p`` streams the whole corpus and counts only part ``p``'s keys in a fresh state,
+        whose own top ``max_f_grams`` is kept on the host; the ``P`` selections are merged into one small state and finalised.
+        Same f-grams, ids and counts.  Device memory is about ``1 / P`` of the streaming route's, the corpus is read ``P``
+        times and at most ``P * max_f_grams`` selection rows are held on the host.  The corpus must give a fresh pass each
+        time: a callable that returns an iterable, or an object whose ``iter()`` starts over (a list, a dataset).  A
+        one-shot iterator raises ``TypeError`` before any device work; passes that differ in their number of n-gram
+        occurrences raise ``RuntimeError``."""
+        if partitions is not None:
+            if int(partitions) < 1:
+                raise ValueError("fit_gpu: partitions must be at least 1")
+            if chunk_tokens is None:
+                raise ValueError("fit_gpu: partitions needs chunk_tokens (the partitioned fit streams the corpus)")
+            if int(partitions) > 1:
+                return self._fit_gpu_partitioned(tokenized_texts, int(chunk_tokens), int(partitions), verbose, device)
         if chunk_tokens is not None:
             return self._fit_gpu_stream(tokenized_texts, int(chunk_tokens), verbose, device)
         import torch
@@ -177,6 +194,38 @@ class NGramExtractor:
                 state.update(tokens, offsets)
                 del tokens, offsets
             self._set_from_finalize(state, self.min_freq, self.max_f_grams)
+        if verbose:
+            print(f"Extracted {len(self)} f-grams")
+        return self
+
+    def _fit_gpu_partitioned(self, tokenized_texts, chunk_tokens: int, n_parts: int, verbose: bool, device) -> "NGramExtractor":
+        """``fit_gpu(partitions=P)``, P > 1.  Exact because a key lives in one part with its whole count and its first
+        number, and a key of the global top ``max_f_grams`` is in the top ``max_f_grams`` of its own part."""
+        from scone_amd import hip_backend
+        if callable(tokenized_texts):
+            fresh = tokenized_texts
+        elif iter(tokenized_texts) is tokenized_texts:
+            raise TypeError("fit_gpu(partitions > 1) reads the corpus once per partition: pass a callable that returns an "
+                            "iterable, or an object whose iter() starts a fresh pass, not a one-shot iterator")
+        else:
+            fresh = lambda: tokenized_texts
+        selections, end = [], None
+        for p in range(n_parts):
+            with hip_backend.FitState(self.max_n, device=device) as state:
+                for tokens, offsets in self._chunks(fresh(), chunk_tokens):
+                    state.update(tokens, offsets, part=p, n_parts=n_parts)
+                    del tokens, offsets
+                next_seq = state.stats()["next_seq"]                  # every occurrence is numbered, counted or not
+                if end is None:
+                    end = next_seq
+                elif next_seq != end:
+                    raise RuntimeError("the corpus changed between passes")
+                keys, klens, counts, _, first = state.finalize(self.min_freq, self.max_f_grams, with_first=True)
+            selections.append((keys, klens, counts, first))
+        with hip_backend.FitState(self.max_n, device=device) as merged:
+            for sel in selections:
+                merged.merge(*sel)
+            self._set_from_finalize(merged, self.min_freq, self.max_f_grams)
         if verbose:
             print(f"Extracted {len(self)} f-grams")
         return self
