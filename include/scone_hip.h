@@ -659,6 +659,60 @@ int scone_ipc_event_record(scone_handle *h, void *event, scone_stream_t stream);
 int scone_ipc_event_wait(scone_handle *h, void *event, scone_stream_t stream);
 int scone_ipc_push(scone_handle *h, void *d_dst, const void *d_src, uint64_t bytes, int32_t copy_engine, scone_stream_t stream);
 
+/* ---- backward: deterministic sparse row gradients of the f-gram table (new here; in the reference the table is a trained
+ * nn.Embedding, f_gram_model.py:120,172, whose gradient autograd scatters with float atomics).  Appended: SCONE_ABI_VERSION
+ * is unchanged.  The gradient needs the id lists and grad_out only and never reads a table row: it works on every row format,
+ * placement and shard.
+ * Definition.  Position p of a batch of ntok positions has the id list L_p, exactly the list scone_embed / scone_embed_varlen /
+ * scone_embed_base* aggregate on this handle: the reference's order (n ascending, start ascending, duplicates kept), every
+ * covering f-gram in cover mode and zero or one id in SCONE_MODE_LONGEST_SUFFIX, only the rows in [row_begin, row_end); K_p is
+ * the FULL hit count.  A reference is a triple (row r, position p, place k in L_p).  Its contribution, all in IEEE fp32 with
+ * g = grad_out: mean  c = fp32(g[p, :]) * w_p, w_p = 1.0f / (float)K_p (one rounded reciprocal per position, one rounded
+ * product per element); sum  c = fp32(g[p, :]).  The references of a row are taken in (p, k) ascending order -- a stable sort by
+ * row of the reference stream -- and cut into chunks of C = scone_backward_chunk() consecutive references.  A chunk's partial
+ * is a = +0.0; a = a + c over its references in order (multiply and add are separate roundings, no fused multiply-add); a row
+ * with one chunk gets that partial, a row with several gets acc = +0.0; acc = acc + partial_j in chunk order.  Output: the U
+ * distinct rows with at least one reference, d_row_ids_out[U] int64 ascending, each row once, and d_grad_rows_out[U, d] fp32 --
+ * the payload of a coalesced torch.sparse_coo_tensor.  No atomics on floating-point data anywhere: the result is a pure function
+ * of the inputs, bit for bit, from run to run.  C is part of that contract: a compile-time power of two in [64, 512].
+ *   scone_backward_chunk         C; no device work
+ *   scone_backward_plan          the lists of scone_embed's batch d_tok [B, T] (matched by the lookup's own matcher; the call
+ *                                stream's workspace is held only while that match and the kernels that read its records are
+ *                                enqueued), expanded to (row, p) pairs, sorted stably by row, cut into chunks.  The plan owns all
+ *                                its buffers -- a later lookup on the same stream does not disturb it -- including the partials
+ *                                buffer of the rows with several chunks: nothing is allocated later.  Synchronises the stream
+ *                                ONCE, to return U in *h_n_rows and the reference count in *h_n_refs (either may be NULL).
+ *                                Token ids out of range: as scone_embed ("Ids out of range": a negative token matches nothing, a
+ *                                token >= vocab matches normally; there is no wte here and no status bit).  B * T == 0 and
+ *                                U == 0 are valid empty plans
+ *   scone_backward_plan_varlen   the same for scone_embed_varlen's packed batch; scone_embed_varlen's refusals apply
+ *   scone_backward_plan_csr      the caller's lists, the counterpart of scone_gather_reduce: d_offsets [ntok + 1] / d_ids int32.
+ *                                K_p is the list length; ids outside the owned range are skipped; ids outside the table are
+ *                                skipped and raise SCONE_ST_BAD_ID (scone_gather_reduce's rule); no such id is ever used as an
+ *                                address, and offsets are clamped into [0, d_offsets[ntok]].  Synchronises once more than the
+ *                                token forms: it first reads d_offsets[ntok], which sizes its buffers
+ *   scone_backward_rows          d_grad_out [ntok, d] in grad_dtype (SCONE_DT_*) -> d_row_ids_out / d_grad_rows_out.  Stream-
+ *                                ordered: no synchronisation, no allocation.  A plan may be used any number of times, with
+ *                                either reduce and any grad_dtype.  rows_cap < U: SCONE_ERANGE, nothing written.  U == 0: a no-op
+ *   scone_backward_counts        K_p per position, int32 [ntok]; stream-ordered
+ *   scone_backward_plan_destroy  NULL: a no-op
+ * SCONE_EINVAL (scone_last_error names the reason): null pointers, a bad grad_dtype / reduce, d % 8 != 0, a handle with
+ * dim == 0, a plan of another handle, a batch whose lists could hold 2^32 references or more.  One plan is used by one host
+ * thread at a time; plans are independent of each other, and a plan must be destroyed before its handle. */
+typedef struct scone_bwd_plan scone_bwd_plan;
+int scone_backward_chunk(void);
+int scone_backward_plan(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, scone_bwd_plan **out, uint64_t *h_n_rows,
+                        uint64_t *h_n_refs, scone_stream_t stream);
+int scone_backward_plan_varlen(scone_handle *h, const int32_t *d_tok, const int32_t *d_cu_seqlens, int32_t n_seqs,
+                               int64_t total_tokens, scone_bwd_plan **out, uint64_t *h_n_rows, uint64_t *h_n_refs,
+                               scone_stream_t stream);
+int scone_backward_plan_csr(scone_handle *h, const int32_t *d_offsets, const int32_t *d_ids, int64_t ntok, scone_bwd_plan **out,
+                            uint64_t *h_n_rows, uint64_t *h_n_refs, scone_stream_t stream);
+int scone_backward_rows(scone_handle *h, scone_bwd_plan *plan, const void *d_grad_out, int32_t grad_dtype, int32_t reduce,
+                        int64_t *d_row_ids_out, float *d_grad_rows_out, uint64_t rows_cap, scone_stream_t stream);
+int scone_backward_counts(scone_handle *h, scone_bwd_plan *plan, int32_t *d_k_out, scone_stream_t stream);
+void scone_backward_plan_destroy(scone_bwd_plan *plan);
+
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
  * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.

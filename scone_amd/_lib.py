@@ -138,6 +138,13 @@ SIGNATURES = {
     "scone_ipc_push": (C.c_int, [_P, _P, _P, _U64, _I32, _P]),
     "scone_finalize": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I64, _I64, _P, _I64, _P, _I64, _P, _I32, _P,
                                  _I32, _P]),
+    "scone_backward_chunk": (C.c_int, []),
+    "scone_backward_plan": (C.c_int, [_P, _P, _I32, _I32, C.POINTER(_P), C.POINTER(_U64), C.POINTER(_U64), _P]),
+    "scone_backward_plan_varlen": (C.c_int, [_P, _P, _P, _I32, _I64, C.POINTER(_P), C.POINTER(_U64), C.POINTER(_U64), _P]),
+    "scone_backward_plan_csr": (C.c_int, [_P, _P, _P, _I64, C.POINTER(_P), C.POINTER(_U64), C.POINTER(_U64), _P]),
+    "scone_backward_rows": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _U64, _P]),
+    "scone_backward_counts": (C.c_int, [_P, _P, _P, _P]),
+    "scone_backward_plan_destroy": (None, [_P]),
 }
 
 _lock = threading.Lock()

@@ -318,6 +318,85 @@ class FitState:
         self._check(rc, "scone_fit_merge")
 
 
+def backward_chunk() -> int:
+    """``scone_backward_chunk``: the chunk length ``C`` of the backward's summation order (part of its contract).  Runs
+    without a GPU."""
+    return int(L.lib().scone_backward_chunk())
+
+
+class BackwardPlan:
+    """``scone_bwd_plan``: the sorted reference stream of one batch on one :class:`SconeTable` (include/scone_hip.h,
+    "backward").  ``n_rows`` distinct rows have at least one of the ``n_refs`` references.  :meth:`rows` may be called any
+    number of times, with either ``reduce`` and any ``grad_out`` dtype; it is stream-ordered and allocates nothing but its
+    outputs.  A context manager; ``close()`` frees the device memory.  Made by :meth:`SconeTable.backward_plan` /
+    :meth:`SconeTable.backward_plan_csr`."""
+
+    def __init__(self, table: "SconeTable", plan, ntok: int, n_rows: int, n_refs: int) -> None:
+        self._table, self._p = table, plan
+        self.ntok, self.n_rows, self.n_refs = int(ntok), int(n_rows), int(n_refs)
+
+    def close(self) -> None:
+        if self._p is not None:
+            L.lib().scone_backward_plan_destroy(self._p)
+            self._p = None
+
+    def __enter__(self) -> "BackwardPlan":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _plan(self):
+        if self._p is None:
+            raise SconeError("BackwardPlan is closed")
+        if self._table._h is None:
+            raise SconeError("BackwardPlan: its table is closed")
+        return self._p
+
+    def rows(self, grad_out: torch.Tensor, reduce: str = "mean",
+             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``scone_backward_rows``: ``(row_ids [U] int64 ascending, grad_rows [U, d] fp32)``, the payload of a coalesced
+        ``torch.sparse_coo_tensor``.  ``grad_out``: ``[ntok, d]`` (or ``[B, T, d]``) fp32 / fp16 / bf16 on the table's device.
+        ``out = (row_ids, grad_rows)``: the caller's buffers of at least ``n_rows`` rows; views of their first ``U`` rows
+        are returned."""
+        plan, t = self._plan(), self._table
+        if grad_out.dtype not in _DT:
+            raise ValueError(f"grad_out must be fp32, fp16 or bf16, not {grad_out.dtype}")
+        if grad_out.numel() != self.ntok * t.dim or (grad_out.dim() and grad_out.shape[-1] != t.dim and grad_out.numel()):
+            raise ValueError(f"grad_out must hold [{self.ntok}, {t.dim}] elements, got {tuple(grad_out.shape)}")
+        if not (grad_out.is_cuda and grad_out.device == t.device and grad_out.is_contiguous()):
+            grad_out = grad_out.to(device=t.device).contiguous()
+        if out is None:
+            ids = torch.empty(self.n_rows, dtype=torch.int64, device=t.device)
+            rows = torch.empty((self.n_rows, t.dim), dtype=torch.float32, device=t.device)
+        else:
+            ids, rows = out
+            assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64 and ids.dim() == 1
+            assert rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.float32 and rows.dim() == 2
+            assert rows.shape[1] == t.dim          # (too few rows: IndexError from the library, nothing written)
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        rc = L.lib().scone_backward_rows(t._h, plan, grad_out.data_ptr(), _DT[grad_out.dtype], _REDUCE[reduce], ids.data_ptr(),
+                                         rows.data_ptr(), min(ids.numel(), rows.shape[0]), stream)
+        t._check(rc, "scone_backward_rows")
+        if self.n_rows:
+            grad_out.record_stream(torch.cuda.current_stream(t.device))    # it may be a temporary of the caller
+        return ids[:self.n_rows], rows[:self.n_rows]
+
+    def counts(self) -> torch.Tensor:
+        """``scone_backward_counts``: ``K_p``, the full hit count of every position, int32 ``[ntok]``."""
+        plan, t = self._plan(), self._table
+        k = torch.empty(self.ntok, dtype=torch.int32, device=t.device)
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        t._check(L.lib().scone_backward_counts(t._h, plan, k.data_ptr(), stream), "scone_backward_counts")
+        return k
+
+
 class SconeTable:
     """Device-resident f-gram index (+ optional table shard)."""
 
@@ -800,6 +879,53 @@ class SconeTable:
         if rc != L.OK:
             self._check(rc, "scone_embed_select")
         return out
+
+    # -- backward ---------------------------------------------------------------
+    def _make_plan(self, rc: int, who: str, plan, ntok: int, n_rows, n_refs) -> BackwardPlan:
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"{who}: {L.lib().scone_last_error(self._h).decode()} "
+                                       f"[{L.lib().scone_strerror(rc).decode()}]")
+        self._check(rc, who)
+        return BackwardPlan(self, plan, ntok, n_rows.value, n_refs.value)
+
+    def backward_plan(self, tok: torch.Tensor, cu_seqlens=None) -> BackwardPlan:
+        """``scone_backward_plan`` / ``scone_backward_plan_varlen``: the plan of the table gradient of the batch :meth:`embed`
+        (``tok [B, T]``) or :meth:`embed_varlen` (``tok [total]`` with ``cu_seqlens``, validated as there) looks up.
+        Synchronises the current stream once."""
+        plan, n_rows, n_refs = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if cu_seqlens is None:
+            tok = self._tok(tok)
+            B, T = tok.shape
+            rc = L.lib().scone_backward_plan(self._h, tok.data_ptr(), B, T, C.byref(plan), C.byref(n_rows), C.byref(n_refs), stream)
+            return self._make_plan(rc, "scone_backward_plan", plan, B * T, n_rows, n_refs)
+        if tok.dim() != 1:
+            raise ValueError("a packed batch takes its token ids as a 1-D tensor [total]")
+        tok = tok.to(device=self.device, dtype=torch.int32).contiguous()
+        total = tok.shape[0]
+        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+            if not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                    and cu_seqlens.numel() >= 1):
+                raise ValueError("a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+            cu = cu_seqlens
+        else:
+            cu = torch.from_numpy(check_cu_seqlens(cu_seqlens, total)).to(self.device)
+        rc = L.lib().scone_backward_plan_varlen(self._h, tok.data_ptr(), cu.data_ptr(), cu.numel() - 1, total, C.byref(plan),
+                                                C.byref(n_rows), C.byref(n_refs), stream)
+        return self._make_plan(rc, "scone_backward_plan_varlen", plan, total if cu.numel() > 1 else 0, n_rows, n_refs)
+
+    def backward_plan_csr(self, offsets: torch.Tensor, ids: torch.Tensor) -> BackwardPlan:
+        """``scone_backward_plan_csr``: the plan of the caller's id lists (``offsets [ntok + 1]``, ``ids``), the counterpart
+        of :meth:`gather_reduce`."""
+        offsets = offsets.to(device=self.device, dtype=torch.int32).contiguous()
+        ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        ntok = max(offsets.numel() - 1, 0)
+        plan, n_rows, n_refs = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = L.lib().scone_backward_plan_csr(self._h, offsets.data_ptr() if offsets.numel() else None,
+                                             ids.data_ptr() if ids.numel() else None, ntok, C.byref(plan), C.byref(n_rows),
+                                             C.byref(n_refs), stream)
+        return self._make_plan(rc, "scone_backward_plan_csr", plan, ntok, n_rows, n_refs)
 
     def embed_prefetch(self, tok: torch.Tensor, tokens_ready: bool = False) -> None:
         """``scone_embed_prefetch``: start the pinned-host prefetch pipeline for ``tok`` (int32 ``[B, T]`` on the device: pass the

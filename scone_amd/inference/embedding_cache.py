@@ -342,6 +342,19 @@ class EmbeddingCache:
             raise IndexError("index out of range in self")
         return result
 
+    def embed_tokens_backward(self, input_ids: torch.Tensor, grad_out: torch.Tensor, *, reduce: str = "mean",
+                              cu_seqlens=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The table gradient of :meth:`embed_tokens` on the same ``input_ids`` (/ ``cu_seqlens``): ``(row_ids [U] int64
+        ascending, grad_rows [U, d] fp32)``, the payload of a coalesced ``torch.sparse_coo_tensor`` over the table's rows.
+        Deterministic (no float atomics; the summation order is part of the C ABI's contract, include/scone_hip.h
+        "backward") and independent of the table format: it reads the id lists and ``grad_out [.., d]`` (fp32 / fp16 /
+        bf16), never a row.  One call plans and reduces; keep :meth:`SconeTable.backward_plan`'s plan to reuse the id
+        lists for several ``grad_out``."""
+        table = self.to_device()
+        # (closing the plan right after the stream-ordered rows call is safe: freeing device memory waits for the device)
+        with table.backward_plan(torch.as_tensor(input_ids), cu_seqlens) as plan:
+            return plan.rows(grad_out, reduce)
+
     def _embed_tokens_base(self, input_ids, base, reduce, wte, wpe, position_ids, out_dtype, out, check, cu_seqlens):
         """``embed_tokens(base=...)``; every ``ValueError`` here is raised before any device work."""
         d = self.embedding_dim

@@ -1,0 +1,104 @@
+"""Training the f-gram table behind the fused lookup.
+
+In the reference the f-gram table is a trained ``nn.Embedding`` (scone/models/f_gram_model.py:120,172) whose output is
+added to the token embeddings (scone/models/language_model.py:239-243).  :class:`TrainableFGramTable` puts the one-launch
+lookup of :class:`~scone_amd.EmbeddingCache` on an autograd tape: the forward is the existing kernel, bit for bit, and the
+backward is the library's deterministic sparse row gradient (include/scone_hip.h, "backward") -- no host synchronise in
+the reduction, no float atomics, the same bits on every run.  The training loop, the optimiser and ``wte`` / ``wpe`` stay
+the caller's torch code, added outside, as language_model.py:239-254 does.
+"""
+
+from typing import Optional
+
+import torch
+from torch import nn
+
+from scone_amd.inference.embedding_cache import EmbeddingCache
+
+
+class _Lookup(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, base, module, input_ids, cu_seqlens, reduce, out_dtype):
+        cache = module.cache
+        tok = torch.as_tensor(input_ids)
+        if base is not None and cache.lookup_mode == "longest_suffix":
+            # the paper's lookup onto a dense base (a matched f-gram REPLACES the base row) is the table's call
+            table = cache.to_device()
+            if cu_seqlens is None:
+                out = table.embed_base(tok, base, reduce=reduce, out_dtype=out_dtype)
+            else:
+                out = table.embed_base_varlen(tok, cu_seqlens, base, reduce=reduce, out_dtype=out_dtype)
+        else:
+            out = cache.embed_tokens(tok, reduce=reduce, base=base, cu_seqlens=cu_seqlens, out_dtype=out_dtype)
+        ctx.module, ctx.tok, ctx.cu, ctx.reduce = module, tok, cu_seqlens, reduce
+        ctx.base_dtype = None if base is None else base.dtype
+        ctx.base_shape = None if base is None else base.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        module = ctx.module
+        table = module.cache.to_device()
+        grad_weight = grad_base = None
+        grad_out = grad_out.contiguous()
+        with table.backward_plan(ctx.tok, ctx.cu) as plan:
+            if ctx.needs_input_grad[0]:
+                row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
+                module._touched.append(row_ids)
+                # set here, not returned: autograd's accumulation re-creates a sparse gradient without its coalesced flag
+                sparse = torch.sparse_coo_tensor(row_ids[None], grad_rows, tuple(module.weight.shape), is_coalesced=True)
+                weight = module.weight
+                weight.grad = sparse if weight.grad is None else (weight.grad + sparse).coalesce()
+            if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
+                grad_base = grad_out
+                if module.cache.lookup_mode == "longest_suffix":     # a matched f-gram replaced the base row
+                    keep = (plan.counts() == 0).reshape(*grad_out.shape[:-1], 1)
+                    grad_base = grad_out * keep
+                grad_base = grad_base.to(ctx.base_dtype).reshape(ctx.base_shape)
+        # (the plan is closed while its kernels may still run: freeing device memory waits for the device)
+        return grad_weight, grad_base, None, None, None, None, None
+
+
+class TrainableFGramTable(nn.Module):
+    """The f-gram table of ``cache`` as a trainable module.
+
+    ``weight`` (fp32 ``[N, d]`` on the table's device, an ``nn.Parameter``) is the master copy; the cache may hold any
+    ``table_format`` -- an INT8 table served from an fp32 master, a folded projection -- because the gradient of the lookup
+    never reads a table row.  ``forward`` runs the existing one-launch lookup (``embed_tokens``, with ``base=`` when given;
+    on a ``lookup_mode="longest_suffix"`` cache with ``base=`` the paper's form, ``cache.table.embed_base``), so its output
+    has the serving path's bits exactly.  ``backward`` sets ``weight.grad`` itself, to a coalesced ``torch.sparse_coo_tensor``
+    (a backward onto a gradient that is already there adds to it and coalesces; ``torch.autograd.grad`` does not see it; use an
+    optimiser that takes sparse gradients: ``SGD``, ``SparseAdam``, ``Adagrad``), and returns ``grad_base = grad_out``
+    (cover mode) or ``grad_out * (K == 0)`` (longest suffix: a matched f-gram replaced the base row).
+    :meth:`commit` re-stores the rows touched since the last commit into the served table, after which it equals a table built
+    from the updated weights.  The cache's host copy of the rows, if it keeps one, is not updated: it is the table at
+    ingestion time."""
+
+    def __init__(self, cache: EmbeddingCache, weight: torch.Tensor) -> None:
+        super().__init__()
+        table = cache.to_device()
+        if not isinstance(weight, nn.Parameter):
+            weight = nn.Parameter(torch.as_tensor(weight).to(device=table.device, dtype=torch.float32).contiguous())
+        if weight.dtype != torch.float32 or tuple(weight.shape) != (table.n_rows, table.dim) or weight.device != table.device:
+            raise ValueError(f"weight must be an fp32 [{table.n_rows}, {table.dim}] parameter on {table.device}")
+        self.cache = cache
+        self.weight = weight
+        self._touched = []
+
+    def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
+                out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        return _Lookup.apply(self.weight, base, self, input_ids, cu_seqlens, reduce, out_dtype)
+
+    @torch.no_grad()
+    def commit(self, ids: Optional[torch.Tensor] = None) -> int:
+        """Re-store ``weight[ids]`` into the served table (``ids=None``: the rows touched by a backward since the last
+        commit -- all an optimiser without momentum or weight decay has changed).  Returns the number of rows stored."""
+        if ids is None:
+            if not self._touched:
+                return 0
+            ids = torch.unique(torch.cat(self._touched))
+        ids = torch.as_tensor(ids).to(device=self.weight.device, dtype=torch.int64).reshape(-1)
+        self._touched = []
+        if ids.numel():
+            self.cache.to_device().store_f32(self.weight.detach()[ids], ids=ids)
+        return int(ids.numel())
