@@ -684,13 +684,18 @@ int scone_ipc_push(scone_handle *h, void *d_dst, const void *d_src, uint64_t byt
  *                                ONCE, to return U in *h_n_rows and the reference count in *h_n_refs (either may be NULL).
  *                                Token ids out of range: as scone_embed ("Ids out of range": a negative token matches nothing, a
  *                                token >= vocab matches normally; there is no wte here and no status bit).  B * T == 0 and
- *                                U == 0 are valid empty plans
- *   scone_backward_plan_varlen   the same for scone_embed_varlen's packed batch; scone_embed_varlen's refusals apply
+ *                                U == 0 are valid empty plans.  On a pinned-host table with stage_tokens > 0 the call works as
+ *                                on any other (it matches and never touches the staging pipeline)
+ *   scone_backward_plan_varlen   the same for scone_embed_varlen's packed batch; scone_embed_varlen's refusals apply (among
+ *                                them stage_tokens > 0: SCONE_EINVAL)
  *   scone_backward_plan_csr      the caller's lists, the counterpart of scone_gather_reduce: d_offsets [ntok + 1] / d_ids int32.
  *                                K_p is the list length; ids outside the owned range are skipped; ids outside the table are
  *                                skipped and raise SCONE_ST_BAD_ID (scone_gather_reduce's rule); no such id is ever used as an
- *                                address, and offsets are clamped into [0, d_offsets[ntok]].  Synchronises once more than the
- *                                token forms: it first reads d_offsets[ntok], which sizes its buffers
+ *                                address, and offsets are clamped into [0, d_offsets[ntok]]: with total = d_offsets[ntok], list p
+ *                                is d_ids[lo, hi), lo = d_offsets[p] clamped into [0, total], hi = d_offsets[p + 1] clamped into
+ *                                [lo, total].  Offsets that decrease give lists that overlap; each is taken as it stands, so
+ *                                the references may outnumber total.  Synchronises twice more than the token forms: it reads
+ *                                d_offsets[ntok], then the number of owned references, which sizes its buffers
  *   scone_backward_rows          d_grad_out [ntok, d] in grad_dtype (SCONE_DT_*) -> d_row_ids_out / d_grad_rows_out.  Stream-
  *                                ordered: no synchronisation, no allocation.  A plan may be used any number of times, with
  *                                either reduce and any grad_dtype.  rows_cap < U: SCONE_ERANGE, nothing written.  U == 0: a no-op

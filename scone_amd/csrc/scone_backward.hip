@@ -106,7 +106,9 @@ __global__ void k_bwd_expand_ell(const int32_t *__restrict__ ell, long long ntok
 }
 
 // the caller's lists: K_p = the list length; ids outside the table raise SCONE_ST_BAD_ID and are skipped, ids outside the owned
-// range are skipped.  Offsets are clamped into [0, total], so no read leaves d_ids[0, total) whatever they hold.
+// range are skipped.  Offsets are clamped into [0, total], so no read leaves d_ids[0, total) whatever they hold.  Clamped lists
+// may overlap (offsets that decrease and rise again), so the owned references of a batch can outnumber `total`: the count
+// kernel adds them up (an integer atomic: the sum does not depend on the order) and that sum sizes the plan.
 __device__ __forceinline__ void csr_range(const int32_t *__restrict__ off, long long p, long long total, long long *b, long long *e) {
   long long lo = off[p], hi = off[p + 1];
   lo = lo < 0 ? 0 : (lo > total ? total : lo);
@@ -116,7 +118,9 @@ __device__ __forceinline__ void csr_range(const int32_t *__restrict__ off, long 
 
 __global__ void k_bwd_count_csr(const int32_t *__restrict__ off, const int32_t *__restrict__ ids, long long ntok, long long total,
                                 long long n_rows, long long row_begin, long long row_end, uint32_t *__restrict__ kown,
-                                int32_t *__restrict__ kfull, float *__restrict__ w, uint32_t *__restrict__ status) {
+                                int32_t *__restrict__ kfull, float *__restrict__ w, uint32_t *__restrict__ status,
+                                unsigned long long *__restrict__ own_total) {
+  unsigned long long mine = 0;  // owned references of this thread's positions: one atomic per wave after the loop
   for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p <= ntok; p += (long long)gridDim.x * blockDim.x) {
     if (p == ntok) {
       kown[p] = 0;
@@ -134,11 +138,16 @@ __global__ void k_bwd_count_csr(const int32_t *__restrict__ off, const int32_t *
         ++own;
     }
     if (bad) atomicOr(status, SCONE_ST_BAD_ID);
+    mine += own;
     const long long kf = e - b;
     kown[p] = own;
     kfull[p] = (int32_t)kf;
     w[p] = kf > 0 ? 1.0f / (float)kf : 1.0f;
   }
+  // every lane of the wave is here (the loop has no early exit); blockDim.x is a multiple of 64
+#pragma unroll
+  for (int step = 32; step > 0; step >>= 1) mine += __shfl_down(mine, step, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(own_total, mine);
 }
 
 __global__ void k_bwd_expand_csr(const int32_t *__restrict__ off, const int32_t *__restrict__ ids, long long ntok, long long total,
@@ -439,13 +448,32 @@ struct plan_src {
   long long csr_total;
 };
 
-// Everything after the argument checks.  `max_refs` is the most references the batch can have.
+// Everything after the argument checks.  `max_refs` is the most references the batch can have; the caller's lists are counted
+// here first (their clamped ranges may overlap, so d_offsets[ntok] bounds nothing) and max_refs becomes the owned count.
 int plan_build(scone_handle *h, scone_bwd_plan *pl, const plan_src &src, unsigned long long max_refs, hipStream_t s) {
   const long long ntok = pl->ntok;
   SCONE_HIP(h, hipMalloc(&pl->d_meta, sizeof(bwd_meta)));
   SCONE_HIP(h, hipMemsetAsync(pl->d_meta, 0, sizeof(bwd_meta), s));
-  if (ntok == 0 || max_refs == 0) {  // an empty plan: no positions, or lists that cannot hold an id
-    if (ntok > 0) {
+  tmp_buf kown, own_total;
+  if (src.kind == BWD_SRC_CSR && ntok > 0) {
+    SCONE_HIP(h, hipMalloc(&pl->d_kfull, (size_t)ntok * 4));
+    SCONE_HIP(h, hipMalloc(&pl->d_w, (size_t)ntok * 4));
+    SCONE_HIP(h, kown.alloc((size_t)(ntok + 1) * 4));
+    SCONE_HIP(h, own_total.alloc(8));
+    SCONE_HIP(h, hipMemsetAsync(own_total.p, 0, 8, s));
+    hipLaunchKernelGGL(k_bwd_count_csr, dim3(blocks_for(ntok + 1)), dim3(BWD_THREADS), 0, s, src.offsets, src.ids, ntok,
+                       src.csr_total, (long long)h->cfg.n_rows, (long long)h->cfg.row_begin, (long long)h->cfg.row_end,
+                       kown.as<uint32_t>(), pl->d_kfull, pl->d_w, h->d_status, own_total.as<unsigned long long>());
+    SCONE_HIP(h, hipGetLastError());
+    unsigned long long owned_refs = 0;
+    SCONE_HIP(h, hipMemcpyAsync(&owned_refs, own_total.p, 8, hipMemcpyDeviceToHost, s));
+    SCONE_HIP(h, hipStreamSynchronize(s));
+    if (owned_refs >= (1ull << 32))
+      return scone_fail(h, SCONE_EINVAL, "scone_backward_plan_csr: too many references for one plan (they are numbered in 32 bits)");
+    max_refs = owned_refs;
+  }
+  if (ntok == 0 || max_refs == 0) {  // an empty plan: no positions, or lists that hold no owned id
+    if (ntok > 0 && !pl->d_kfull) {
       SCONE_HIP(h, hipMalloc(&pl->d_kfull, (size_t)ntok * 4));
       SCONE_HIP(h, hipMemsetAsync(pl->d_kfull, 0, (size_t)ntok * 4, s));
     }
@@ -460,15 +488,15 @@ int plan_build(scone_handle *h, scone_bwd_plan *pl, const plan_src &src, unsigne
   const uint32_t pad_key = (uint32_t)n_rows;
   const int end_bit = bits_for(n_rows + 1);
 
-  SCONE_HIP(h, hipMalloc(&pl->d_kfull, (size_t)ntok * 4));
-  SCONE_HIP(h, hipMalloc(&pl->d_w, (size_t)ntok * 4));
+  if (!pl->d_kfull) SCONE_HIP(h, hipMalloc(&pl->d_kfull, (size_t)ntok * 4));
+  if (!pl->d_w) SCONE_HIP(h, hipMalloc(&pl->d_w, (size_t)ntok * 4));
   SCONE_HIP(h, hipMalloc(&pl->d_ref_p, (size_t)max_refs * 4));
   SCONE_HIP(h, hipMalloc(&pl->d_row_id, (size_t)(seg_cap + 1) * 4));
   SCONE_HIP(h, hipMalloc(&pl->d_chunks, (size_t)chunk_cap * sizeof(bwd_chunk)));
   SCONE_HIP(h, hipMalloc(&pl->d_multi, (size_t)multi_cap * sizeof(bwd_multi)));
 
-  tmp_buf kown, ref_off, keys, keys2, vals, flags, incl, seg_start, nch, ch_base, nmulti, multi_base, scratch;
-  SCONE_HIP(h, kown.alloc((size_t)(ntok + 1) * 4));
+  tmp_buf ref_off, keys, keys2, vals, flags, incl, seg_start, nch, ch_base, nmulti, multi_base, scratch;
+  if (!kown.p) SCONE_HIP(h, kown.alloc((size_t)(ntok + 1) * 4));
   SCONE_HIP(h, ref_off.alloc((size_t)(ntok + 1) * 4));
   SCONE_HIP(h, keys.alloc((size_t)max_refs * 4));
   SCONE_HIP(h, keys2.alloc((size_t)max_refs * 4));
@@ -500,11 +528,7 @@ int plan_build(scone_handle *h, scone_bwd_plan *pl, const plan_src &src, unsigne
   SCONE_HIP(h, scratch.alloc(need));
 
   // (1) id lists -> K_own / K_full / w per position, the reference offsets, the (row, p) pairs in (p, k) order
-  if (src.kind == BWD_SRC_CSR) {
-    hipLaunchKernelGGL(k_bwd_count_csr, dim3(blocks_for(ntok + 1)), dim3(BWD_THREADS), 0, s, src.offsets, src.ids, ntok,
-                       src.csr_total, (long long)n_rows, (long long)h->cfg.row_begin, (long long)h->cfg.row_end, kown.as<uint32_t>(),
-                       pl->d_kfull, pl->d_w, h->d_status);
-    SCONE_HIP(h, hipGetLastError());
+  if (src.kind == BWD_SRC_CSR) {  // counted above
     n1 = need;
     SCONE_HIP(h, rocprim::exclusive_scan(scratch.p, n1, kown.as<uint32_t>(), ref_off.as<uint32_t>(), 0u, (size_t)(ntok + 1),
                                          rocprim::plus<uint32_t>(), s));

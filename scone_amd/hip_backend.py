@@ -916,7 +916,12 @@ class SconeTable:
 
     def backward_plan_csr(self, offsets: torch.Tensor, ids: torch.Tensor) -> BackwardPlan:
         """``scone_backward_plan_csr``: the plan of the caller's id lists (``offsets [ntok + 1]``, ``ids``), the counterpart
-        of :meth:`gather_reduce`."""
+        of :meth:`gather_reduce`.  Host ``offsets`` are checked here: ``offsets[-1]`` (the library reads no id at or beyond it)
+        must lie in ``[0, ids.numel()]``.  Device ``offsets`` are trusted, as a device ``cu_seqlens`` is."""
+        if not offsets.is_cuda and offsets.numel():
+            total = int(offsets.reshape(-1)[-1])
+            if total < 0 or total > ids.numel():
+                raise ValueError(f"backward_plan_csr: offsets[-1] = {total} is outside [0, ids.numel() = {ids.numel()}]")
         offsets = offsets.to(device=self.device, dtype=torch.int32).contiguous()
         ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
         ntok = max(offsets.numel() - 1, 0)

@@ -16,6 +16,30 @@ from torch import nn
 from scone_amd.inference.embedding_cache import EmbeddingCache
 
 
+def _add_coalesced(old: torch.Tensor, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> torch.Tensor:
+    """``old + sparse(row_ids, grad_rows)`` as a coalesced sparse tensor, without ``torch``'s ``coalesce()``, which is wrong
+    for wide values with torch 2.10.0+rocm7.0 on gfx950.  Torch alone shows it (profiles/r17a/torch_coalesce_wide_values.txt):
+    with 25 sorted ids and fp32 ``a``, ``b`` ``[25, d]`` on the device,
+    ``torch.sparse_coo_tensor(torch.cat([ids, ids])[None], torch.cat([a, b]), (60, d)).coalesce().values()`` equals ``a + b``
+    at d = 64 and 256, and differs in 228 of 512, 456 of 768 (all zero from column 312 on) and 684 of 1024 columns;
+    ``(sa + sb).coalesce()`` of the two coalesced tensors gives the same.  So no path here calls it.  ``row_ids`` are sorted
+    and distinct; a row both operands have is ``old + new`` (one fp32 add), a row one has is that row, bit for bit.  An
+    ``old`` that is not coalesced (set by the caller) has its duplicates added first, by ``index_add_``."""
+    old_ids, old_rows = old._indices()[0], old._values()
+    ids, inverse = torch.unique(torch.cat([old_ids, row_ids]), return_inverse=True)         # sorted
+    at_old, at_new = inverse[:old_ids.numel()], inverse[old_ids.numel():]
+    rows = torch.zeros((ids.numel(), grad_rows.shape[1]), dtype=grad_rows.dtype, device=grad_rows.device)
+    if old.is_coalesced():
+        rows.index_copy_(0, at_old, old_rows)
+    else:
+        rows.index_add_(0, at_old, old_rows)
+    in_old = torch.zeros(ids.numel(), dtype=torch.bool, device=ids.device)
+    in_old[at_old] = True
+    both = in_old[at_new]
+    rows.index_copy_(0, at_new, torch.where(both[:, None], rows[at_new] + grad_rows, grad_rows))
+    return torch.sparse_coo_tensor(ids[None], rows, tuple(old.shape), is_coalesced=True)
+
+
 class _Lookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, base, module, input_ids, cu_seqlens, reduce, out_dtype):
@@ -48,7 +72,7 @@ class _Lookup(torch.autograd.Function):
                 # set here, not returned: autograd's accumulation re-creates a sparse gradient without its coalesced flag
                 sparse = torch.sparse_coo_tensor(row_ids[None], grad_rows, tuple(module.weight.shape), is_coalesced=True)
                 weight = module.weight
-                weight.grad = sparse if weight.grad is None else (weight.grad + sparse).coalesce()
+                weight.grad = sparse if weight.grad is None else _add_coalesced(weight.grad, row_ids, grad_rows)
             if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
                 grad_base = grad_out
                 if module.cache.lookup_mode == "longest_suffix":     # a matched f-gram replaced the base row
