@@ -718,6 +718,53 @@ int scone_backward_rows(scone_handle *h, scone_bwd_plan *plan, const void *d_gra
 int scone_backward_counts(scone_handle *h, scone_bwd_plan *plan, int32_t *d_k_out, scone_stream_t stream);
 void scone_backward_plan_destroy(scone_bwd_plan *plan);
 
+/* ---- optimizer step: the fused sparse update of the fp32 master rows, their optimizer state and the served table (new here;
+ * the reference trains the table with a stock torch optimizer).  Appended: SCONE_ABI_VERSION is unchanged.  It consumes what
+ * scone_backward_rows returns: d_row_ids [n] int64 ascending and distinct, d_grad_rows [n, d] fp32.
+ * Arrays.  d_master, d_state1, d_state2: fp32 [row_end - row_begin, d] on the handle's device, indexed by id - row_begin (the
+ * handle's owned rows).  d_state1 is Adam's m; d_state2 is Adam's v or Adagrad's sum of squares; an array the kind does not use
+ * may be NULL.  All three are updated in place.
+ * Scalars.  scone_opt_scalars_of computes them on the host in double and rounds each to fp32 ONCE (no GPU, no handle):
+ *   alpha = lr (SGD, Adagrad);  alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t) (Adam, t = step >= 1)
+ *   b1 = beta1, b2 = beta2, c1 = 1 - beta1, c2 = 1 - beta2, eps = eps, decay = lr * weight_decay, gscale = grad_scale
+ * scone_opt_step uses exactly these values; a test that wants the bits reads them here (as C from scone_backward_chunk).
+ * Per element (g of d_grad_rows, w of d_master, m / v / s of the state), every operation IEEE fp32 and rounded once, NO fused
+ * multiply-add, sqrt and / correctly rounded, subnormals kept -- the translation unit is built with the Makefile's flags
+ * (-ffp-contract=off, nothing else: correctly rounded sqrt and division and IEEE subnormals are hipcc's defaults for gfx950):
+ *   g1 = gscale == 1 ? g : g * gscale
+ *   w1 = decay  == 0 ? w : w - decay * w                   (decoupled and lazy: only the listed rows decay)
+ *   SGD      w' = w1 - alpha * g1
+ *   ADAGRAD  s' = s + g1 * g1 ;                             w' = w1 - (alpha * g1) / (sqrt(s') + eps)
+ *   ADAM     m' = b1 * m + c1 * g1 ; v' = b2 * v + c2 * (g1 * g1) ; w' = w1 - (alpha * m') / (sqrt(v') + eps)
+ * gscale == 1 and decay == 0 skip their step exactly (no multiply by 1, no subtraction of 0 * w).
+ * Served table.  Global row id of the handle's table becomes exactly what scone_table_store_f32_ids of the w' row would have
+ * stored: every format and its scales (the d == 1024 scale-slot orders of INT4 / MXFP4 included), HBM or a pinned-host table
+ * with a hot head, a row-sharded handle.  As with that call, a staged-prefetch cache (stage_tokens > 0), if one exists, is
+ * dropped first.  A row that is not listed keeps every bit: master, state and table.
+ * Ids.  An id outside [row_begin, row_end) is skipped and raises SCONE_ST_BAD_ID; an id <= its predecessor in the list is
+ * skipped and raises SCONE_ST_BAD_ID; no such id is ever used as an address.  Every other row is applied, by one wavefront,
+ * independent of every other.  (A list that repeats a row at a distance is outside the contract: both copies are applied, in
+ * no order; nothing outside that row is touched.)
+ * The call is stream-ordered: it does not synchronise, allocates nothing and does all its device work in ONE kernel launch
+ * (grid capped as every row-parallel kernel here; environment SCONE_OPT_MAX_BLOCKS, read by scone_create, lowers the cap).
+ * n == 0: a no-op.  Plain vector stores only; no atomics but the integer OR on the status word: a pure function of its inputs.
+ * SCONE_EINVAL (scone_last_error names the reason): null cfg / d_row_ids / d_grad_rows / d_master, a state array the kind
+ * needs is NULL, a bad kind or struct_size, step < 1 for Adam, a non-finite lr / beta1 / beta2 / eps / weight_decay /
+ * grad_scale, a handle with dim == 0. */
+enum { SCONE_OPT_SGD = 0, SCONE_OPT_ADAGRAD = 1, SCONE_OPT_ADAM = 2 };
+typedef struct scone_opt_cfg {
+  uint32_t struct_size; /* sizeof(scone_opt_cfg) */
+  int32_t kind;         /* SCONE_OPT_* */
+  double lr, beta1, beta2, eps, weight_decay, grad_scale; /* grad_scale 1.0 and weight_decay 0.0: that step is skipped exactly */
+  int64_t step;         /* t >= 1: Adam's bias correction; ignored by the others */
+} scone_opt_cfg;
+typedef struct scone_opt_scalars {
+  float alpha, b1, b2, c1, c2, eps, decay, gscale;
+} scone_opt_scalars;
+int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars *out);
+int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
+                   float *d_master, float *d_state1, float *d_state2, scone_stream_t stream);
+
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
  * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.

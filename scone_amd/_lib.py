@@ -46,6 +46,29 @@ class SconeCfg(C.Structure):
     ]
 
 
+OPT_SGD, OPT_ADAGRAD, OPT_ADAM = 0, 1, 2
+
+
+class OptCfg(C.Structure):
+    """``scone_opt_cfg``: the hyper-parameters of one optimizer step, in double."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("kind", C.c_int32),
+        ("lr", C.c_double),
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("eps", C.c_double),
+        ("weight_decay", C.c_double),
+        ("grad_scale", C.c_double),
+        ("step", C.c_int64),
+    ]
+
+
+class OptScalars(C.Structure):
+    """``scone_opt_scalars``: the fp32 values the kernel computes with (``scone_opt_scalars_of``)."""
+    _fields_ = [(name, C.c_float) for name in ("alpha", "b1", "b2", "c1", "c2", "eps", "decay", "gscale")]
+
+
 _P = C.c_void_p
 _I32, _I64, _U32, _U64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 
@@ -145,6 +168,8 @@ SIGNATURES = {
     "scone_backward_rows": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _U64, _P]),
     "scone_backward_counts": (C.c_int, [_P, _P, _P, _P]),
     "scone_backward_plan_destroy": (None, [_P]),
+    "scone_opt_scalars_of": (C.c_int, [C.POINTER(OptCfg), C.POINTER(OptScalars)]),
+    "scone_opt_step": (C.c_int, [_P, C.POINTER(OptCfg), _P, _P, _U64, _P, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

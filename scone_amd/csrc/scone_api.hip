@@ -287,6 +287,9 @@ extern "C" int scone_create(const scone_cfg *cfg, scone_handle **out) {
     h->varlen_t = 0;  // 0: the packed stream is one row (measured best: scone_embed_varlen, scone_gather.hip)
     ev = getenv("SCONE_VARLEN_T");
     if (ev && *ev && atoll(ev) > 0 && atoll(ev) <= 0x7FFFFFFFll) h->varlen_t = atoll(ev);
+    h->opt_max_blocks = 0;  // 0: scone_capped_blocks; a small cap lets a test walk the optimizer step's grid-stride loop
+    ev = getenv("SCONE_OPT_MAX_BLOCKS");
+    if (ev && *ev && atoll(ev) > 0 && atoll(ev) <= (long long)SCONE_MAX_BLOCKS) h->opt_max_blocks = atoll(ev);
   }
   CREATE_HIP(hipMalloc(&h->slots, cap * sizeof(scone_slot)));
   CREATE_HIP(hipMemset(h->slots, 0, cap * sizeof(scone_slot)));

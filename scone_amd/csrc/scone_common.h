@@ -187,6 +187,7 @@ struct scone_handle {
   long long fused_max_tokens;  // batches up to this many tokens take the one-launch kernel (env SCONE_FUSED_MAX_TOKENS overrides)
   long long match_tile;        // > 0: positions per workgroup of k_match_ell fixed by env SCONE_MATCH_TILE (else whole residency rounds)
   long long varlen_t;          // > 0: row length T' of the packed lookup's gather traversal [total / T', T'] + remainder, fixed by env SCONE_VARLEN_T
+  long long opt_max_blocks;    // > 0: grid cap of scone_opt_step fixed by env SCONE_OPT_MAX_BLOCKS (else scone_capped_blocks)
   // index
   scone_slot *slots;
   uint64_t cap;  // power of two

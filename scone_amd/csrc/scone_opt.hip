@@ -1,0 +1,295 @@
+// The fused sparse optimizer step (include/scone_hip.h, "optimizer step"): for every listed row, one wave reads the gradient
+// row, the fp32 master row and the optimizer state, writes the updated master row and state in place and stores the row into
+// the served table in the table's format -- exactly the bytes scone_table_store_f32_ids of the updated row would store.
+//
+// Shape.  One wave owns a row; lane l owns the 16-byte pieces l, l + 64, .. of every stream.  A row is walked in blocks of
+// OPT_NT * 64 pieces (1024 elements): the loads of all streams of a block are issued before its arithmetic.  fp32 / fp16 / bf16
+// rows are stored element by element.  INT4 groups (128 elements = 32 lanes of one piece pass) and MXFP4 blocks (32 elements =
+// 8 lanes) have their maximum inside one pass: __shfl_xor over that many lanes, then the payload.  INT8 needs the maximum of the
+// whole row before its first payload byte: rows of up to 1024 elements stay in registers (one block); wider rows are stored to
+// the master first and read back, every lane reading only the pieces it stored itself -- no lane ever depends on another
+// lane's global store.  The maxima are exact (no rounding), so the bits cannot depend on which lanes hold which elements.
+//
+// Arithmetic.  Every operation is one IEEE fp32 rounding: the library is built with -ffp-contract=off and nothing here calls
+// fmaf; sqrtf and / are hipcc's correctly rounded defaults and subnormals are kept (tests/test_gpu_opt_step.py pins all of it).
+// The element arithmetic of every row format is scone_quant.h's, shared with k_store_f32 (scone_table.hip); the GPU tests hold the
+// two kernels together on every format.  Plain vector stores only; the one atomic is the integer atomicOr on the status word.
+#include "scone_common.h"
+#include "scone_quant.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int OPT_NT = 4;  // pieces per lane and block: 4 x 64 x 4 = 1024 elements
+
+__device__ __forceinline__ float opt_wave_max(float v) {
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+  return v;
+}
+
+// one element: the contract's statement, one rounding per operation
+template <int KIND>
+__device__ __forceinline__ void opt_elem(const scone_opt_scalars &k, float g, float &w, float &m, float &v) {
+  const float g1 = k.gscale == 1.0f ? g : g * k.gscale;
+  float w1 = w;
+  if (k.decay != 0.0f) {
+    const float dw = k.decay * w;
+    w1 = w - dw;
+  }
+  if (KIND == SCONE_OPT_SGD) {
+    const float s = k.alpha * g1;
+    w = w1 - s;
+  } else if (KIND == SCONE_OPT_ADAGRAD) {
+    const float gg = g1 * g1;
+    v = v + gg;
+    const float num = k.alpha * g1;
+    const float den = sqrtf(v) + k.eps;
+    w = w1 - num / den;
+  } else {
+    const float a = k.b1 * m, b = k.c1 * g1;
+    m = a + b;
+    const float gg = g1 * g1;
+    const float c = k.b2 * v, e = k.c2 * gg;
+    v = c + e;
+    const float num = k.alpha * m;
+    const float den = sqrtf(v) + k.eps;
+    w = w1 - num / den;
+  }
+}
+
+__device__ __forceinline__ uint32_t opt_i8_word(const float4 &x, float sf) {
+  const float xs[4] = {x.x, x.y, x.z, x.w};
+  uint32_t word = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) word |= (uint32_t)(uint8_t)(int8_t)(int)scone_q_elem(xs[k], sf, 127.f) << (8 * k);
+  return word;
+}
+
+// The served-table bytes of piece p (elements 4p .. 4p + 3) of local row lr for the formats whose scale, if any, is known
+// inside one piece pass.  Every lane of the wave calls this (the group maxima are shuffles); `on` guards the stores.
+template <int FMT>
+__device__ __forceinline__ void opt_store_piece(const scone_row_store &st, __half *__restrict__ scales, unsigned long long lr, int d,
+                                                int p, bool on, const float4 &x, int lane) {
+  uint8_t *row = st.row(lr);
+  if (FMT == SCONE_FMT_F32) {
+    if (on) reinterpret_cast<float4 *>(row)[p] = x;
+  } else if (FMT == SCONE_FMT_F16) {
+    const uint32_t a = __half_as_ushort(__float2half_rn(x.x)), b = __half_as_ushort(__float2half_rn(x.y));
+    const uint32_t c = __half_as_ushort(__float2half_rn(x.z)), e = __half_as_ushort(__float2half_rn(x.w));
+    if (on) reinterpret_cast<uint2 *>(row)[p] = make_uint2(a | (b << 16), c | (e << 16));
+  } else if (FMT == SCONE_FMT_BF16) {
+    if (on)
+      reinterpret_cast<uint2 *>(row)[p] =
+          make_uint2((uint32_t)scone_f32_to_bf16_bits(x.x) | ((uint32_t)scone_f32_to_bf16_bits(x.y) << 16),
+                     (uint32_t)scone_f32_to_bf16_bits(x.z) | ((uint32_t)scone_f32_to_bf16_bits(x.w) << 16));
+  } else if (FMT == SCONE_FMT_I4) {  // a group of 128 elements is 32 lanes of this pass
+    float m = fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w)));
+    for (int s = 16; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+    const __half sh = scone_q_scale(m, 7.0f);
+    const float sf = __half2float(sh);
+    const int q[4] = {(int)scone_q_elem(x.x, sf, 7.f), (int)scone_q_elem(x.y, sf, 7.f), (int)scone_q_elem(x.z, sf, 7.f),
+                      (int)scone_q_elem(x.w, sf, 7.f)};
+    const uint32_t b0 = (uint32_t)((q[0] + 8) | ((q[1] + 8) << 4)) & 0xFFu, b1 = (uint32_t)((q[2] + 8) | ((q[3] + 8) << 4)) & 0xFFu;
+    if (on) {
+      reinterpret_cast<unsigned short *>(row)[p] = (unsigned short)(b0 | (b1 << 8));
+      if ((lane & 31) == 0) scales[lr * (unsigned long long)(d / SCONE_I4_GROUP) + scone_i4_scale_slot(p >> 5, d)] = sh;
+    }
+  } else if (FMT == SCONE_FMT_MXFP4) {  // a block of 32 elements is 8 lanes of this pass
+    const uint32_t uu[4] = {__float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z), __float_as_uint(x.w)};
+    uint32_t m = max(max(uu[0] & 0x7FFFFFFFu, uu[1] & 0x7FFFFFFFu), max(uu[2] & 0x7FFFFFFFu, uu[3] & 0x7FFFFFFFu));
+    for (int s = 4; s >= 1; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
+    const uint32_t X = scone_mx_block_scale(m);
+    const uint32_t nib[4] = {scone_mx_nibble(uu[0], X), scone_mx_nibble(uu[1], X), scone_mx_nibble(uu[2], X), scone_mx_nibble(uu[3], X)};
+    if (on) {
+      reinterpret_cast<unsigned short *>(row)[p] = (unsigned short)(nib[0] | (nib[1] << 4) | (nib[2] << 8) | (nib[3] << 12));
+      if ((lane & 7) == 0)
+        reinterpret_cast<uint8_t *>(scales)[lr * (unsigned long long)(d / SCONE_MX_BLOCK) + scone_mx_scale_slot(p >> 3, d)] = (uint8_t)X;
+    }
+  }
+}
+
+// One wave per listed row; the grid-stride loop over rows is k_store_f32's.
+template <int FMT, int KIND>
+__global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ ids, const float *__restrict__ grad,
+                                                  unsigned long long n, unsigned long long row_begin, unsigned long long row_end,
+                                                  int d, scone_opt_scalars sc, float *__restrict__ master, float *__restrict__ state1,
+                                                  float *__restrict__ state2, scone_row_store st, __half *__restrict__ scales,
+                                                  uint32_t *__restrict__ status) {
+  constexpr bool HAS_M = KIND == SCONE_OPT_ADAM;
+  constexpr bool HAS_V = KIND != SCONE_OPT_SGD;
+  const int lane = threadIdx.x & 63;
+  const int pieces = d >> 2;
+  const unsigned long long nwaves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+  for (unsigned long long r = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < n; r += nwaves) {
+    const long long id = ids[r];
+    // wave-uniform: outside the owned range, or not above its predecessor in the list -> skipped, never an address
+    if ((unsigned long long)id < row_begin || (unsigned long long)id >= row_end || (r > 0 && id <= ids[r - 1])) {
+      if (lane == 0) atomicOr(status, SCONE_ST_BAD_ID);
+      continue;
+    }
+    const unsigned long long lr = (unsigned long long)id - row_begin;
+    const float4 *G = reinterpret_cast<const float4 *>(grad + r * (unsigned long long)d);
+    float4 *W = reinterpret_cast<float4 *>(master + lr * (unsigned long long)d);
+    float4 *M = HAS_M ? reinterpret_cast<float4 *>(state1 + lr * (unsigned long long)d) : nullptr;
+    float4 *V = HAS_V ? reinterpret_cast<float4 *>(state2 + lr * (unsigned long long)d) : nullptr;
+    float rowmax = 0.f;  // INT8 only
+    for (int p0 = 0; p0 < pieces; p0 += OPT_NT * 64) {
+      float4 g[OPT_NT], w[OPT_NT], m[OPT_NT], v[OPT_NT];
+      bool on[OPT_NT];
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) {
+        const int p = p0 + t * 64 + lane;
+        on[t] = p < pieces;
+        g[t] = w[t] = m[t] = v[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (on[t]) {
+          g[t] = G[p];
+          w[t] = W[p];
+          if (HAS_M) m[t] = M[p];
+          if (HAS_V) v[t] = V[p];
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) {
+        opt_elem<KIND>(sc, g[t].x, w[t].x, m[t].x, v[t].x);
+        opt_elem<KIND>(sc, g[t].y, w[t].y, m[t].y, v[t].y);
+        opt_elem<KIND>(sc, g[t].z, w[t].z, m[t].z, v[t].z);
+        opt_elem<KIND>(sc, g[t].w, w[t].w, m[t].w, v[t].w);
+      }
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) {
+        const int p = p0 + t * 64 + lane;
+        if (on[t]) {
+          W[p] = w[t];
+          if (HAS_M) M[p] = m[t];
+          if (HAS_V) V[p] = v[t];
+        }
+        if (FMT == SCONE_FMT_I8) {
+          if (on[t]) rowmax = fmaxf(rowmax, fmaxf(fmaxf(fabsf(w[t].x), fabsf(w[t].y)), fmaxf(fabsf(w[t].z), fabsf(w[t].w))));
+        } else if (p0 + t * 64 < pieces) {  // wave-uniform: a pass with no piece at all has no shuffles either
+          opt_store_piece<FMT>(st, scales, lr, d, p, on[t], w[t], lane);
+        }
+      }
+      if (FMT == SCONE_FMT_I8 && pieces <= OPT_NT * 64) {  // the whole row is in registers
+        const __half sh = scone_q_scale(opt_wave_max(rowmax), 127.0f);
+        const float sf = __half2float(sh);
+        uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
+#pragma unroll
+        for (int t = 0; t < OPT_NT; ++t)
+          if (on[t]) o[p0 + t * 64 + lane] = opt_i8_word(w[t], sf);
+        if (lane == 0) scales[lr] = sh;
+      }
+    }
+    if (FMT == SCONE_FMT_I8 && pieces > OPT_NT * 64) {  // a wide row: read back what THIS lane stored above
+      const __half sh = scone_q_scale(opt_wave_max(rowmax), 127.0f);
+      const float sf = __half2float(sh);
+      uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
+      for (int p0 = 0; p0 < pieces; p0 += OPT_NT * 64) {
+        float4 x[OPT_NT];
+#pragma unroll
+        for (int t = 0; t < OPT_NT; ++t) {
+          const int p = p0 + t * 64 + lane;
+          if (p < pieces) x[t] = W[p];
+        }
+#pragma unroll
+        for (int t = 0; t < OPT_NT; ++t) {
+          const int p = p0 + t * 64 + lane;
+          if (p < pieces) o[p] = opt_i8_word(x[t], sf);
+        }
+      }
+      if (lane == 0) scales[lr] = sh;
+    }
+  }
+}
+
+const char *opt_check(const scone_opt_cfg *cfg) {
+  if (!cfg) return "null cfg";
+  if (cfg->struct_size != sizeof(scone_opt_cfg)) return "cfg.struct_size does not match this library";
+  if (cfg->kind != SCONE_OPT_SGD && cfg->kind != SCONE_OPT_ADAGRAD && cfg->kind != SCONE_OPT_ADAM) return "bad kind";
+  if (!std::isfinite(cfg->lr) || !std::isfinite(cfg->beta1) || !std::isfinite(cfg->beta2) || !std::isfinite(cfg->eps) ||
+      !std::isfinite(cfg->weight_decay) || !std::isfinite(cfg->grad_scale))
+    return "lr, beta1, beta2, eps, weight_decay and grad_scale must be finite";
+  if (cfg->kind == SCONE_OPT_ADAM && cfg->step < 1) return "Adam needs step >= 1";
+  return nullptr;
+}
+
+void opt_scalars(const scone_opt_cfg *cfg, scone_opt_scalars *out) {
+  double alpha = cfg->lr;
+  if (cfg->kind == SCONE_OPT_ADAM) {
+    const double t = (double)cfg->step;
+    alpha = cfg->lr * std::sqrt(1.0 - std::pow(cfg->beta2, t)) / (1.0 - std::pow(cfg->beta1, t));
+  }
+  out->alpha = (float)alpha;
+  out->b1 = (float)cfg->beta1;
+  out->b2 = (float)cfg->beta2;
+  out->c1 = (float)(1.0 - cfg->beta1);
+  out->c2 = (float)(1.0 - cfg->beta2);
+  out->eps = (float)cfg->eps;
+  out->decay = (float)(cfg->lr * cfg->weight_decay);
+  out->gscale = (float)cfg->grad_scale;
+}
+
+struct opt_args {
+  const int64_t *ids;
+  const float *grad;
+  unsigned long long n;
+  scone_opt_scalars sc;
+  float *master, *s1, *s2;
+};
+
+template <int FMT, int KIND>
+void opt_launch(scone_handle *h, const opt_args &a, unsigned blocks, hipStream_t s) {
+  hipLaunchKernelGGL((k_opt_step<FMT, KIND>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, a.n, (unsigned long long)h->cfg.row_begin,
+                     (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2, scone_store_of(h),
+                     (__half *)h->scales, h->d_status);
+}
+
+template <int FMT>
+void opt_launch_kind(scone_handle *h, int kind, const opt_args &a, unsigned blocks, hipStream_t s) {
+  if (kind == SCONE_OPT_SGD)
+    opt_launch<FMT, SCONE_OPT_SGD>(h, a, blocks, s);
+  else if (kind == SCONE_OPT_ADAGRAD)
+    opt_launch<FMT, SCONE_OPT_ADAGRAD>(h, a, blocks, s);
+  else
+    opt_launch<FMT, SCONE_OPT_ADAM>(h, a, blocks, s);
+}
+
+}  // namespace
+
+extern "C" int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars *out) {
+  if (!out || opt_check(cfg)) return SCONE_EINVAL;
+  opt_scalars(cfg, out);
+  return SCONE_OK;
+}
+
+extern "C" int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
+                              float *d_master, float *d_state1, float *d_state2, scone_stream_t stream) {
+  if (!h) return SCONE_EINVAL;
+  if (const char *bad = opt_check(cfg)) return scone_fail(h, SCONE_EINVAL, (std::string("scone_opt_step: ") + bad).c_str());
+  if (h->cfg.dim == 0) return scone_fail(h, SCONE_EINVAL, "scone_opt_step: handle has no table (dim == 0)");
+  if (!h->rows) return scone_fail(h, SCONE_ESTATE, "scone_opt_step: handle has no table");
+  if (n == 0) return SCONE_OK;
+  if (!d_row_ids || !d_grad_rows || !d_master) return scone_fail(h, SCONE_EINVAL, "scone_opt_step: null pointer");
+  if (cfg->kind == SCONE_OPT_ADAM && !d_state1) return scone_fail(h, SCONE_EINVAL, "scone_opt_step: Adam needs d_state1 (m)");
+  if (cfg->kind != SCONE_OPT_SGD && !d_state2)
+    return scone_fail(h, SCONE_EINVAL, "scone_opt_step: Adam / Adagrad need d_state2 (v / the sum of squares)");
+  SCONE_ON_DEVICE(h);
+  if (h->stage) scone_stage_destroy(h);  // the table changes: as scone_table_store_f32_ids (the staged cache of cold rows is dropped)
+  opt_args a;
+  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2;
+  opt_scalars(cfg, &a.sc);
+  unsigned blocks = scone_capped_blocks((n + 3) / 4);
+  if (h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks) blocks = (unsigned)h->opt_max_blocks;
+  hipStream_t s = (hipStream_t)stream;
+  switch (h->cfg.table_fmt) {
+    case SCONE_FMT_F32: opt_launch_kind<SCONE_FMT_F32>(h, cfg->kind, a, blocks, s); break;
+    case SCONE_FMT_F16: opt_launch_kind<SCONE_FMT_F16>(h, cfg->kind, a, blocks, s); break;
+    case SCONE_FMT_I8: opt_launch_kind<SCONE_FMT_I8>(h, cfg->kind, a, blocks, s); break;
+    case SCONE_FMT_I4: opt_launch_kind<SCONE_FMT_I4>(h, cfg->kind, a, blocks, s); break;
+    case SCONE_FMT_BF16: opt_launch_kind<SCONE_FMT_BF16>(h, cfg->kind, a, blocks, s); break;
+    case SCONE_FMT_MXFP4: opt_launch_kind<SCONE_FMT_MXFP4>(h, cfg->kind, a, blocks, s); break;
+    default: return scone_fail(h, SCONE_EINVAL, "scone_opt_step: bad format");
+  }
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}

@@ -10,6 +10,7 @@
 // tests/bf16_fixture.py to_bf16_bits, that of the MXFP4 quantiser tests/mxfp4_fixture.py quantize (the format itself:
 // include/scone_hip.h).
 #include "scone_common.h"
+#include "scone_quant.h"
 
 #include <type_traits>
 
@@ -18,16 +19,6 @@ namespace {
 __device__ __forceinline__ float wave_max(float v) {
   for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
   return v;
-}
-
-// fp32 -> bfloat16 bits, IEEE round-to-nearest-even: a tie (low half 0x8000) goes to the even upper half, a finite value
-// beyond the largest bf16 carries into the exponent and becomes +-inf, fp32 subnormals round into bf16 subnormals, -0.0 and
-// +-inf pass through.  NaN is taken out first: the increment would carry a NaN with a high payload into the sign bit
-// (0x7FFFFFFF -> 0x8000 = -0.0) and a truncation could leave the infinity's 0x7F80; it stays a NaN with the quiet bit set.
-__device__ __forceinline__ unsigned short f32_to_bf16_bits(float x) {
-  const uint32_t u = __float_as_uint(x);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x0040u);
-  return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
 // One wave per row.  src row index = blockIdx-derived r; destination local row =
@@ -56,26 +47,19 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
     for (int e = lane; e < d; e += 64) o[e] = __float2half_rn(x[e]);
   } else if (FMT == SCONE_FMT_BF16) {
     unsigned short *o = reinterpret_cast<unsigned short *>(st.row(lr));
-    for (int e = lane; e < d; e += 64) o[e] = f32_to_bf16_bits(x[e]);
+    for (int e = lane; e < d; e += 64) o[e] = scone_f32_to_bf16_bits(x[e]);
   } else if (FMT == SCONE_FMT_I8) {
     float m = 0.f;
     for (int e = lane; e < d; e += 64) m = fmaxf(m, fabsf(x[e]));
     m = wave_max(m);
-    const __half sh = __float2half_rn(m / 127.0f);
+    const __half sh = scone_q_scale(m, 127.0f);
     const float sf = __half2float(sh);
     int8_t *o = reinterpret_cast<int8_t *>(st.row(lr));
-    for (int e = lane; e < d; e += 64) {
-      float q = 0.f;
-      if (sf > 0.f) q = fminf(fmaxf(rintf(x[e] / sf), -127.f), 127.f);
-      o[e] = (int8_t)(int)q;
-    }
+    for (int e = lane; e < d; e += 64) o[e] = (int8_t)(int)scone_q_elem(x[e], sf, 127.f);
     if (lane == 0) scales[lr] = sh;
   } else if (FMT == SCONE_FMT_MXFP4) {
-    // 128 elements per pass: lane l holds elements 2l, 2l + 1 (one payload byte), 16 lanes share a block of 32.
-    // OCP MX v1.0: a NaN / inf in the block -> X = 255; else X = max(0, exponent field of amax - 2) (amax = 0: 127), which is
-    // clamp(floor(log2 amax) - 2 + 127, 0, 254) -- a subnormal amax has field 0, FLT_MAX 254 -> 252.  q = |v| 2^(127-X) is exact
-    // (a power-of-two scaling; where it underflows it is far below the first midpoint), and the comparisons below are
-    // round-to-nearest with ties to the even code: 0.25 -> 0, 0.75 -> 1.0, 1.25 -> 1.0, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4.
+    // 128 elements per pass: lane l holds elements 2l, 2l + 1 (one payload byte), 16 lanes share a block of 32; the scale and
+    // the rounding of an element are scone_quant.h's
     const int nb = d / SCONE_MX_BLOCK;
     uint8_t *o = st.row(lr);
     uint8_t *sc = reinterpret_cast<uint8_t *>(scales);
@@ -83,18 +67,8 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
       const uint32_t ua = __float_as_uint(x[grp * 128 + 2 * lane]), ub = __float_as_uint(x[grp * 128 + 2 * lane + 1]);
       uint32_t m = max(ua & 0x7FFFFFFFu, ub & 0x7FFFFFFFu);
       for (int sh = 8; sh >= 1; sh >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, sh, 64));
-      const uint32_t X = m >= 0x7F800000u ? 255u : (m == 0u ? 127u : ((m >> 23) > 2u ? (m >> 23) - 2u : 0u));
-      uint32_t nib[2];
-      const uint32_t uu[2] = {ua, ub};
-      for (int k = 0; k < 2; ++k) {
-        uint32_t code = 0;
-        if (X != 255u) {
-          const float q = __uint_as_float(uu[k] & 0x7FFFFFFFu) * __uint_as_float((254u - X) << 23);
-          code = (q > 0.25f) + (q >= 0.75f) + (q > 1.25f) + (q >= 1.75f) + (q > 2.5f) + (q >= 3.5f) + (q > 5.0f);
-        }
-        nib[k] = code | ((uu[k] >> 31) << 3);
-      }
-      o[grp * 64 + lane] = (uint8_t)(nib[0] | (nib[1] << 4));
+      const uint32_t X = scone_mx_block_scale(m);
+      o[grp * 64 + lane] = (uint8_t)(scone_mx_nibble(ua, X) | (scone_mx_nibble(ub, X) << 4));
       if ((lane & 15) == 0) sc[lr * nb + scone_mx_scale_slot(grp * 4 + (lane >> 4), d)] = (uint8_t)X;
     }
   } else {  // I4: groups of 128, two elements per lane per group
@@ -104,13 +78,9 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
       const float a = x[grp * SCONE_I4_GROUP + 2 * lane];
       const float b = x[grp * SCONE_I4_GROUP + 2 * lane + 1];
       const float m = wave_max(fmaxf(fabsf(a), fabsf(b)));
-      const __half sh = __float2half_rn(m / 7.0f);
+      const __half sh = scone_q_scale(m, 7.0f);
       const float sf = __half2float(sh);
-      int qa = 0, qb = 0;
-      if (sf > 0.f) {
-        qa = (int)fminf(fmaxf(rintf(a / sf), -7.f), 7.f);
-        qb = (int)fminf(fmaxf(rintf(b / sf), -7.f), 7.f);
-      }
+      const int qa = (int)scone_q_elem(a, sf, 7.f), qb = (int)scone_q_elem(b, sf, 7.f);
       o[grp * (SCONE_I4_GROUP / 2) + lane] = (uint8_t)((qa + 8) | ((qb + 8) << 4));
       if (lane == 0) scales[lr * ng + scone_i4_scale_slot(grp, d)] = sh;
     }
@@ -182,7 +152,7 @@ __global__ __launch_bounds__(256) void k_fill_synth(unsigned long long row_begin
         for (int k = 0; k < 4; ++k) o[k] = __float2half_rn(v[k]);
       } else if (FMT == SCONE_FMT_BF16) {
         unsigned short *o = reinterpret_cast<unsigned short *>(st.row(lr)) + 4 * w;
-        for (int k = 0; k < 4; ++k) o[k] = f32_to_bf16_bits(v[k]);  // the same fp32 value the fp32 / fp16 tables round
+        for (int k = 0; k < 4; ++k) o[k] = scone_f32_to_bf16_bits(v[k]);  // the same fp32 value the fp32 / fp16 tables round
       }
     }
   }

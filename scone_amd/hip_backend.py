@@ -324,6 +324,29 @@ def backward_chunk() -> int:
     return int(L.lib().scone_backward_chunk())
 
 
+_OPT = {"sgd": L.OPT_SGD, "adagrad": L.OPT_ADAGRAD, "adam": L.OPT_ADAM}
+
+
+def _opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step) -> "L.OptCfg":
+    if isinstance(kind, str):
+        if kind.lower() not in _OPT:
+            raise ValueError(f"unknown optimizer kind {kind!r} (sgd, adagrad, adam)")
+        kind = _OPT[kind.lower()]
+    return L.OptCfg(C.sizeof(L.OptCfg), int(kind), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                    float(grad_scale), int(step))
+
+
+def opt_scalars(kind, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, step=1) -> dict:
+    """``scone_opt_scalars_of``: the fp32 scalars ``scone_opt_step`` computes with (``alpha, b1, b2, c1, c2, eps, decay,
+    gscale``, each an ``np.float32``), from hyper-parameters given in double.  Runs without a GPU; ``ValueError`` for what
+    the library refuses (a bad kind, ``step < 1`` for Adam, a value that is not finite)."""
+    out = L.OptScalars()
+    rc = L.lib().scone_opt_scalars_of(C.byref(_opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step)), C.byref(out))
+    if rc != L.OK:
+        _raise(rc, "scone_opt_scalars_of: bad kind, step < 1 for Adam, or a hyper-parameter that is not finite")
+    return {name: np.float32(getattr(out, name)) for name, _ in L.OptScalars._fields_}
+
+
 class BackwardPlan:
     """``scone_bwd_plan``: the sorted reference stream of one batch on one :class:`SconeTable` (include/scone_hip.h,
     "backward").  ``n_rows`` distinct rows have at least one of the ``n_refs`` references.  :meth:`rows` may be called any
@@ -931,6 +954,43 @@ class SconeTable:
                                              ids.data_ptr() if ids.numel() else None, ntok, C.byref(plan), C.byref(n_rows),
                                              C.byref(n_refs), stream)
         return self._make_plan(rc, "scone_backward_plan_csr", plan, ntok, n_rows, n_refs)
+
+    def opt_step(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, master: torch.Tensor, *, kind, lr: float, step: int = 1,
+                 state1: Optional[torch.Tensor] = None, state2: Optional[torch.Tensor] = None, betas=(0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0) -> None:
+        """``scone_opt_step``: the fused sparse optimizer step (include/scone_hip.h, "optimizer step").  ``row_ids`` ``[U]``
+        int64 ascending and distinct and ``grad_rows`` ``[U, d]`` fp32 are what :meth:`BackwardPlan.rows` returns.  ``master``,
+        ``state1`` (Adam's m) and ``state2`` (Adam's v / Adagrad's sum of squares) are fp32 ``[row_end - row_begin, d]``,
+        contiguous, on the table's device: the rows this handle owns, updated in place; the served table receives the updated
+        rows in its own format.  ``kind``: ``"sgd"``, ``"adagrad"`` or ``"adam"``.  One kernel launch on the current stream; no
+        synchronisation."""
+        cfg = _opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step)
+        owned = self.row_end - self.row_begin
+        for name, t, needed in (("master", master, True), ("state1", state1, cfg.kind == L.OPT_ADAM),
+                                ("state2", state2, cfg.kind in (L.OPT_ADAM, L.OPT_ADAGRAD))):
+            if t is None:
+                if needed:
+                    raise ValueError(f"opt_step: this kind needs {name}")
+                continue
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (owned, self.dim)
+                    and t.device == self.device and t.is_contiguous()):
+                raise ValueError(f"opt_step: {name} must be a contiguous fp32 [{owned}, {self.dim}] tensor on {self.device} "
+                                 "(it is updated in place)")
+        if row_ids.dim() != 1 or grad_rows.dim() != 2 or grad_rows.shape[0] != row_ids.numel() or grad_rows.shape[1] != self.dim:
+            raise ValueError(f"opt_step: row_ids [U] and grad_rows [U, {self.dim}], got {tuple(row_ids.shape)} and "
+                             f"{tuple(grad_rows.shape)}")
+        if row_ids.dtype != torch.int64 or grad_rows.dtype != torch.float32:
+            raise ValueError("opt_step: row_ids must be int64 and grad_rows fp32")
+        row_ids = row_ids.to(device=self.device).contiguous()
+        grad_rows = grad_rows.to(device=self.device).contiguous()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_opt_step(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
+                                        _ptr(state1), _ptr(state2), stream.cuda_stream)
+        self._check(rc, "scone_opt_step")
+        if row_ids.numel():                                        # they may be temporaries of the caller
+            row_ids.record_stream(stream)
+            grad_rows.record_stream(stream)
 
     def embed_prefetch(self, tok: torch.Tensor, tokens_ready: bool = False) -> None:
         """``scone_embed_prefetch``: start the pinned-host prefetch pipeline for ``tok`` (int32 ``[B, T]`` on the device: pass the

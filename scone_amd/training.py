@@ -4,8 +4,10 @@ In the reference the f-gram table is a trained ``nn.Embedding`` (scone/models/f_
 added to the token embeddings (scone/models/language_model.py:239-243).  :class:`TrainableFGramTable` puts the one-launch
 lookup of :class:`~scone_amd.EmbeddingCache` on an autograd tape: the forward is the existing kernel, bit for bit, and the
 backward is the library's deterministic sparse row gradient (include/scone_hip.h, "backward") -- no host synchronise in
-the reduction, no float atomics, the same bits on every run.  The training loop, the optimiser and ``wte`` / ``wpe`` stay
-the caller's torch code, added outside, as language_model.py:239-254 does.
+the reduction, no float atomics, the same bits on every run.  The training loop and ``wte`` / ``wpe`` stay the caller's
+torch code, added outside, as language_model.py:239-254 does.  The table's own update is either a stock ``torch.optim``
+sparse step followed by :meth:`TrainableFGramTable.commit`, or :class:`FGramOptimizer`: one kernel launch that updates the
+touched master rows, their optimizer state and the served table (include/scone_hip.h, "optimizer step").
 """
 
 from typing import Optional
@@ -92,7 +94,8 @@ class TrainableFGramTable(nn.Module):
     on a ``lookup_mode="longest_suffix"`` cache with ``base=`` the paper's form, ``cache.table.embed_base``), so its output
     has the serving path's bits exactly.  ``backward`` sets ``weight.grad`` itself, to a coalesced ``torch.sparse_coo_tensor``
     (a backward onto a gradient that is already there adds to it and coalesces; ``torch.autograd.grad`` does not see it; use an
-    optimiser that takes sparse gradients: ``SGD``, ``SparseAdam``, ``Adagrad``), and returns ``grad_base = grad_out``
+    optimiser that takes sparse gradients: ``SGD``, ``SparseAdam``, ``Adagrad`` -- or :class:`FGramOptimizer`, which updates
+    the served table in the same launch), and returns ``grad_base = grad_out``
     (cover mode) or ``grad_out * (K == 0)`` (longest suffix: a matched f-gram replaced the base row).
     :meth:`commit` re-stores the rows touched since the last commit into the served table, after which it equals a table built
     from the updated weights.  The cache's host copy of the rows, if it keeps one, is not updated: it is the table at
@@ -126,3 +129,92 @@ class TrainableFGramTable(nn.Module):
         if ids.numel():
             self.cache.to_device().store_f32(self.weight.detach()[ids], ids=ids)
         return int(ids.numel())
+
+
+class FGramOptimizer:
+    """The fused sparse optimizer of a :class:`TrainableFGramTable` (include/scone_hip.h, "optimizer step").
+
+    ``step()`` consumes ``module.weight.grad`` -- the coalesced sparse gradient the backward set -- and in ONE kernel launch
+    updates the touched rows of ``module.weight``, their optimizer state and the served table, so the next forward reads the
+    updated rows and ``module.commit()`` has nothing left to store.  ``kind``: ``"sgd"``, ``"adagrad"`` or ``"adam"`` (the
+    arithmetic of ``torch.optim.SparseAdam``: lazy moments, bias correction folded into the step size); ``weight_decay`` is
+    decoupled and lazy (only the touched rows decay).  Adam's ``m`` / ``v`` and Adagrad's sum of squares are fp32 ``[N, d]``
+    on the table's device, allocated at the first step.  ``lr`` is a plain attribute: change it between steps (schedules are
+    the caller's).  No host synchronisation, no ``coalesce()``; the same bits on every run."""
+
+    def __init__(self, module: TrainableFGramTable, kind: str = "adam", lr: float = 1e-3, betas=(0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 0.0) -> None:
+        if kind not in ("sgd", "adagrad", "adam"):
+            raise ValueError(f"unknown optimizer kind {kind!r} (sgd, adagrad, adam)")
+        self.module, self.kind = module, kind
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.t = 0
+        self.state1: Optional[torch.Tensor] = None     # Adam's m
+        self.state2: Optional[torch.Tensor] = None     # Adam's v / Adagrad's sum of squares
+
+    def _ensure_state(self) -> None:
+        w = self.module.weight
+        if self.kind == "adam" and self.state1 is None:
+            self.state1 = torch.zeros_like(w.detach(), memory_format=torch.contiguous_format)
+        if self.kind in ("adam", "adagrad") and self.state2 is None:
+            self.state2 = torch.zeros_like(w.detach(), memory_format=torch.contiguous_format)
+
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0) -> int:
+        """One update from ``module.weight.grad`` (``None``: nothing happens, ``t`` stays).  ``grad_scale`` multiplies the
+        gradient first (an un-scaling of a loss scale, a 1 / accumulation count).  Returns the number of rows updated."""
+        module = self.module
+        weight, grad = module.weight, module.weight.grad
+        if grad is None:
+            return 0
+        if not grad.is_sparse:
+            raise ValueError("FGramOptimizer.step: module.weight.grad must be the sparse gradient the lookup's backward sets")
+        if not grad.is_coalesced():                      # set by the caller: its duplicates are added first, never by coalesce()
+            none = torch.zeros(0, dtype=torch.int64, device=grad.device)
+            grad = _add_coalesced(grad, none, torch.zeros((0, weight.shape[1]), dtype=grad.dtype, device=grad.device))
+        row_ids, grad_rows = grad._indices()[0], grad._values()
+        table = module.cache.to_device()
+        lo, hi = table.row_begin, table.row_end
+        self.t += 1
+        self._ensure_state()
+
+        def own(x):                                      # the rows this handle owns: a contiguous view
+            return None if x is None else x[lo:hi]
+
+        table.opt_step(row_ids, grad_rows, own(weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
+                       state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                       grad_scale=grad_scale)
+        module._touched = []                             # the served table is current: commit() has nothing to store
+        return int(row_ids.numel())
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        grad = self.module.weight.grad
+        if grad is None:
+            return
+        if set_to_none:
+            self.module.weight.grad = None
+        else:
+            shape = tuple(self.module.weight.shape)
+            self.module.weight.grad = torch.sparse_coo_tensor(
+                torch.zeros((1, 0), dtype=torch.int64, device=grad.device),
+                torch.zeros((0, shape[1]), dtype=grad.dtype, device=grad.device), shape, is_coalesced=True)
+
+    def state_dict(self) -> dict:
+        return {"kind": self.kind, "t": self.t, "lr": self.lr, "betas": self.betas, "eps": self.eps,
+                "weight_decay": self.weight_decay,
+                "state1": None if self.state1 is None else self.state1.clone(),
+                "state2": None if self.state2 is None else self.state2.clone()}
+
+    def load_state_dict(self, state: dict) -> None:
+        if state["kind"] != self.kind:
+            raise ValueError(f"state of a {state['kind']!r} optimizer loaded into a {self.kind!r} one")
+        self.t, self.lr, self.eps, self.weight_decay = int(state["t"]), float(state["lr"]), float(state["eps"]), float(state["weight_decay"])
+        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        w = self.module.weight
+        for name in ("state1", "state2"):
+            s = state[name]
+            if s is not None:
+                if tuple(s.shape) != tuple(w.shape):
+                    raise ValueError(f"{name} must be [{w.shape[0]}, {w.shape[1]}], got {tuple(s.shape)}")
+                s = s.to(device=w.device, dtype=torch.float32).contiguous().clone()
+            setattr(self, name, s)
