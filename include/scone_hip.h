@@ -765,6 +765,71 @@ int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars *out);
 int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
                    float *d_master, float *d_state1, float *d_state2, scone_stream_t stream);
 
+/* ---- lean optimizer step: training a table that is too large for scone_opt_step's fp32 [N, d] master and state arrays (new
+ * here).  Appended: SCONE_ABI_VERSION is unchanged; scone_opt_step and scone_opt_cfg are as they were.  Two changes make the
+ * memory small: ROW-WISE Adagrad keeps ONE fp32 accumulator per row (d_row_state, fp32 [row_end - row_begin], indexed by
+ * id - row_begin) instead of one per element, and IN-PLACE mode has no master copy at all: the served fp32 / bf16 rows are
+ * the weights.  A 100M x 1024 bf16 table is 205 GB of rows + 0.4 GB of state; scone_opt_step's Adam needs 1.2 TB beside it.
+ * d_row_ids [n] int64 and d_grad_rows [n, d] fp32 are what scone_backward_rows returns, as for scone_opt_step.
+ * Modes.
+ *   master mode (d_master != NULL): d_master is fp32 [row_end - row_begin, d] as in scone_opt_step; the master row is updated
+ *     in place and the served row becomes exactly what scone_table_store_f32_ids of the new master row stores -- every format
+ *     and every placement scone_opt_step supports.  SCONE_LEAN_SGD here equals scone_opt_step's SGD bit for bit.
+ *   in-place mode (d_master == NULL): w is the stored element widened to fp32 (fp32: the value; bf16: bits << 16), read and
+ *     written through the handle's own row store (HBM, pinned host with a hot head, an owned shard range).  SCONE_FMT_F32 and
+ *     SCONE_FMT_BF16 tables only: every other format returns SCONE_EINVAL naming it (a quantised row cannot hold a small
+ *     update; fp16 is left out on purpose).
+ * Scalars.  scone_lean_scalars_of (no GPU, no handle) fills alpha = lr, eps = eps, decay = lr * weight_decay, gscale =
+ * grad_scale, each computed in double and rounded to fp32 ONCE; the other fields of scone_opt_scalars are 0.
+ * Per element, every operation IEEE fp32 and rounded once, NO fused multiply-add, sqrt and / correctly rounded, subnormals kept
+ * (the unit is built with the Makefile's flags, as scone_opt_step's is):
+ *   g1 = gscale == 1 ? g : g * gscale
+ *   w1 = decay  == 0 ? w : w - decay * w
+ *   SGD              w' = w1 - alpha * g1
+ *   ROWWISE_ADAGRAD  q  = row sum of g1 * g1 (order below);  g2 = q / (float)d;  s' = s + g2   (one s per row)
+ *                    den = sqrtf(s') + eps;                   w'_j = w1_j - (alpha * g1_j) / den
+ * Row sum order (part of the contract).  Element j belongs to lane l = (j / 4) % 64.  Each lane starts at q_l = +0.0f and adds
+ * its elements in ascending j as q_l = q_l + (g1_j * g1_j): the product is rounded first, then the sum.  A lane with no element
+ * holds +0.0f.  Then, for s = 32, 16, 8, 4, 2, 1:  q_l = q_l + q_(l ^ s), all lanes at once.  Every lane ends with the same bits
+ * (fp32 addition is commutative and each stage pairs l with l ^ s); that value is q.
+ * Rounding of the stored row (in-place bf16 only; cfg.rounding).
+ *   SCONE_ROUND_NEAREST     round-to-nearest-even, the table's own fp32 -> bf16 conversion.
+ *   SCONE_ROUND_STOCHASTIC  u = the fp32 bits of w'.  Exponent field all ones (inf / NaN): as nearest.  Otherwise the stored
+ *     bits are (u + r) >> 16 in 32-bit arithmetic, r = scone_lean_rand16(seed, step, GLOBAL row id, j) in [0, 65536).  A value
+ *     bf16 holds exactly never changes; both signs round away from zero with probability frac / 65536, so the rounding is
+ *     unbiased; a carry out of the largest finite value gives infinity, as round-to-nearest's does.
+ *   SCONE_ROUND_STOCHASTIC with a master, or on an fp32 table: SCONE_EINVAL (there is nothing to round).
+ * Random bits.  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (32-bit).  h = 0x9E3779B9;
+ * h = mix(h ^ v) for v = seed low, seed high, step low, step high, row low, row high, col in turn; r = h >> 16.  Keyed by the
+ * GLOBAL row id and the column, never by list position, wave, grid or shard: the bits of a row do not depend on the batch,
+ * the grid cap or how the table is sharded.  cfg.seed and cfg.step feed these bits and nothing else.  scone_lean_rand16 is
+ * the host copy of the device function (no GPU, no handle).
+ * Ids: scone_opt_step's rules.  An id outside [row_begin, row_end) is skipped and raises SCONE_ST_BAD_ID; an id <= its
+ * predecessor in the list is skipped and raises SCONE_ST_BAD_ID; no such id is ever used as an address.  A row that is not
+ * listed keeps every bit: table row, master and row state.
+ * The call is stream-ordered: no synchronisation, no allocation, all device work in ONE kernel launch (grid capped as
+ * scone_opt_step's; SCONE_OPT_MAX_BLOCKS applies).  A staged-prefetch cache is dropped first.  n == 0: a no-op.  Plain vector
+ * stores only; no atomics but the integer OR on the status word.
+ * SCONE_EINVAL (scone_last_error names the reason): a null cfg / d_row_ids / d_grad_rows, a null d_row_state for row-wise
+ * Adagrad, a bad kind, rounding or struct_size, reserved != 0, a non-finite lr / eps / weight_decay / grad_scale, a handle
+ * with dim == 0, the mode and format refusals above. */
+enum { SCONE_LEAN_SGD = 0, SCONE_LEAN_ROWWISE_ADAGRAD = 1 };
+enum { SCONE_ROUND_NEAREST = 0, SCONE_ROUND_STOCHASTIC = 1 };
+typedef struct scone_lean_cfg {
+  uint32_t struct_size; /* sizeof(scone_lean_cfg) */
+  int32_t kind;         /* SCONE_LEAN_* */
+  int32_t rounding;     /* SCONE_ROUND_* */
+  int32_t reserved;     /* 0 */
+  double lr, eps, weight_decay, grad_scale;
+  uint64_t seed;        /* feed the random bits only */
+  int64_t step;
+} scone_lean_cfg;
+int scone_lean_scalars_of(const scone_lean_cfg *cfg, scone_opt_scalars *out);
+uint32_t scone_lean_rand16(uint64_t seed, int64_t step, uint64_t row_id, uint32_t col);
+int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                        uint64_t n, float *d_master /* NULL: in place */, float *d_row_state /* fp32 [row_end - row_begin] */,
+                        scone_stream_t stream);
+
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
  * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.

@@ -69,6 +69,26 @@ class OptScalars(C.Structure):
     _fields_ = [(name, C.c_float) for name in ("alpha", "b1", "b2", "c1", "c2", "eps", "decay", "gscale")]
 
 
+LEAN_SGD, LEAN_ROWWISE_ADAGRAD = 0, 1
+ROUND_NEAREST, ROUND_STOCHASTIC = 0, 1
+
+
+class LeanCfg(C.Structure):
+    """``scone_lean_cfg``: the hyper-parameters of one lean optimizer step; ``seed`` / ``step`` feed the random bits only."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("kind", C.c_int32),
+        ("rounding", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lr", C.c_double),
+        ("eps", C.c_double),
+        ("weight_decay", C.c_double),
+        ("grad_scale", C.c_double),
+        ("seed", C.c_uint64),
+        ("step", C.c_int64),
+    ]
+
+
 _P = C.c_void_p
 _I32, _I64, _U32, _U64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 
@@ -170,6 +190,9 @@ SIGNATURES = {
     "scone_backward_plan_destroy": (None, [_P]),
     "scone_opt_scalars_of": (C.c_int, [C.POINTER(OptCfg), C.POINTER(OptScalars)]),
     "scone_opt_step": (C.c_int, [_P, C.POINTER(OptCfg), _P, _P, _U64, _P, _P, _P, _P]),
+    "scone_lean_scalars_of": (C.c_int, [C.POINTER(LeanCfg), C.POINTER(OptScalars)]),
+    "scone_lean_rand16": (_U32, [_U64, _I64, _U64, _U32]),
+    "scone_opt_step_lean": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _U64, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

@@ -15,18 +15,12 @@
 // The element arithmetic of every row format is scone_quant.h's, shared with k_store_f32 (scone_table.hip); the GPU tests hold the
 // two kernels together on every format.  Plain vector stores only; the one atomic is the integer atomicOr on the status word.
 #include "scone_common.h"
+#include "scone_opt_rows.h"  // the row stores shared with k_opt_lean
 #include "scone_quant.h"
 
 #include <cmath>
 
 namespace {
-
-constexpr int OPT_NT = 4;  // pieces per lane and block: 4 x 64 x 4 = 1024 elements
-
-__device__ __forceinline__ float opt_wave_max(float v) {
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
 
 // one element: the contract's statement, one rounding per operation
 template <int KIND>
@@ -55,57 +49,6 @@ __device__ __forceinline__ void opt_elem(const scone_opt_scalars &k, float g, fl
     const float num = k.alpha * m;
     const float den = sqrtf(v) + k.eps;
     w = w1 - num / den;
-  }
-}
-
-__device__ __forceinline__ uint32_t opt_i8_word(const float4 &x, float sf) {
-  const float xs[4] = {x.x, x.y, x.z, x.w};
-  uint32_t word = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) word |= (uint32_t)(uint8_t)(int8_t)(int)scone_q_elem(xs[k], sf, 127.f) << (8 * k);
-  return word;
-}
-
-// The served-table bytes of piece p (elements 4p .. 4p + 3) of local row lr for the formats whose scale, if any, is known
-// inside one piece pass.  Every lane of the wave calls this (the group maxima are shuffles); `on` guards the stores.
-template <int FMT>
-__device__ __forceinline__ void opt_store_piece(const scone_row_store &st, __half *__restrict__ scales, unsigned long long lr, int d,
-                                                int p, bool on, const float4 &x, int lane) {
-  uint8_t *row = st.row(lr);
-  if (FMT == SCONE_FMT_F32) {
-    if (on) reinterpret_cast<float4 *>(row)[p] = x;
-  } else if (FMT == SCONE_FMT_F16) {
-    const uint32_t a = __half_as_ushort(__float2half_rn(x.x)), b = __half_as_ushort(__float2half_rn(x.y));
-    const uint32_t c = __half_as_ushort(__float2half_rn(x.z)), e = __half_as_ushort(__float2half_rn(x.w));
-    if (on) reinterpret_cast<uint2 *>(row)[p] = make_uint2(a | (b << 16), c | (e << 16));
-  } else if (FMT == SCONE_FMT_BF16) {
-    if (on)
-      reinterpret_cast<uint2 *>(row)[p] =
-          make_uint2((uint32_t)scone_f32_to_bf16_bits(x.x) | ((uint32_t)scone_f32_to_bf16_bits(x.y) << 16),
-                     (uint32_t)scone_f32_to_bf16_bits(x.z) | ((uint32_t)scone_f32_to_bf16_bits(x.w) << 16));
-  } else if (FMT == SCONE_FMT_I4) {  // a group of 128 elements is 32 lanes of this pass
-    float m = fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w)));
-    for (int s = 16; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
-    const __half sh = scone_q_scale(m, 7.0f);
-    const float sf = __half2float(sh);
-    const int q[4] = {(int)scone_q_elem(x.x, sf, 7.f), (int)scone_q_elem(x.y, sf, 7.f), (int)scone_q_elem(x.z, sf, 7.f),
-                      (int)scone_q_elem(x.w, sf, 7.f)};
-    const uint32_t b0 = (uint32_t)((q[0] + 8) | ((q[1] + 8) << 4)) & 0xFFu, b1 = (uint32_t)((q[2] + 8) | ((q[3] + 8) << 4)) & 0xFFu;
-    if (on) {
-      reinterpret_cast<unsigned short *>(row)[p] = (unsigned short)(b0 | (b1 << 8));
-      if ((lane & 31) == 0) scales[lr * (unsigned long long)(d / SCONE_I4_GROUP) + scone_i4_scale_slot(p >> 5, d)] = sh;
-    }
-  } else if (FMT == SCONE_FMT_MXFP4) {  // a block of 32 elements is 8 lanes of this pass
-    const uint32_t uu[4] = {__float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z), __float_as_uint(x.w)};
-    uint32_t m = max(max(uu[0] & 0x7FFFFFFFu, uu[1] & 0x7FFFFFFFu), max(uu[2] & 0x7FFFFFFFu, uu[3] & 0x7FFFFFFFu));
-    for (int s = 4; s >= 1; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
-    const uint32_t X = scone_mx_block_scale(m);
-    const uint32_t nib[4] = {scone_mx_nibble(uu[0], X), scone_mx_nibble(uu[1], X), scone_mx_nibble(uu[2], X), scone_mx_nibble(uu[3], X)};
-    if (on) {
-      reinterpret_cast<unsigned short *>(row)[p] = (unsigned short)(nib[0] | (nib[1] << 4) | (nib[2] << 8) | (nib[3] << 12));
-      if ((lane & 7) == 0)
-        reinterpret_cast<uint8_t *>(scales)[lr * (unsigned long long)(d / SCONE_MX_BLOCK) + scone_mx_scale_slot(p >> 3, d)] = (uint8_t)X;
-    }
   }
 }
 
@@ -165,40 +108,14 @@ __global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ id
           if (HAS_V) V[p] = v[t];
         }
         if (FMT == SCONE_FMT_I8) {
-          if (on[t]) rowmax = fmaxf(rowmax, fmaxf(fmaxf(fabsf(w[t].x), fabsf(w[t].y)), fmaxf(fabsf(w[t].z), fabsf(w[t].w))));
+          if (on[t]) rowmax = opt_i8_amax(rowmax, w[t]);
         } else if (p0 + t * 64 < pieces) {  // wave-uniform: a pass with no piece at all has no shuffles either
           opt_store_piece<FMT>(st, scales, lr, d, p, on[t], w[t], lane);
         }
       }
-      if (FMT == SCONE_FMT_I8 && pieces <= OPT_NT * 64) {  // the whole row is in registers
-        const __half sh = scone_q_scale(opt_wave_max(rowmax), 127.0f);
-        const float sf = __half2float(sh);
-        uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
-#pragma unroll
-        for (int t = 0; t < OPT_NT; ++t)
-          if (on[t]) o[p0 + t * 64 + lane] = opt_i8_word(w[t], sf);
-        if (lane == 0) scales[lr] = sh;
-      }
+      if (FMT == SCONE_FMT_I8 && pieces <= OPT_NT * 64) opt_i8_store_block(st, scales, lr, p0, lane, on, w, rowmax);  // the row is in registers
     }
-    if (FMT == SCONE_FMT_I8 && pieces > OPT_NT * 64) {  // a wide row: read back what THIS lane stored above
-      const __half sh = scone_q_scale(opt_wave_max(rowmax), 127.0f);
-      const float sf = __half2float(sh);
-      uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
-      for (int p0 = 0; p0 < pieces; p0 += OPT_NT * 64) {
-        float4 x[OPT_NT];
-#pragma unroll
-        for (int t = 0; t < OPT_NT; ++t) {
-          const int p = p0 + t * 64 + lane;
-          if (p < pieces) x[t] = W[p];
-        }
-#pragma unroll
-        for (int t = 0; t < OPT_NT; ++t) {
-          const int p = p0 + t * 64 + lane;
-          if (p < pieces) o[p] = opt_i8_word(x[t], sf);
-        }
-      }
-      if (lane == 0) scales[lr] = sh;
-    }
+    if (FMT == SCONE_FMT_I8 && pieces > OPT_NT * 64) opt_i8_store_wide(st, scales, lr, W, pieces, lane, rowmax);
   }
 }
 

@@ -1,0 +1,297 @@
+// The lean optimizer step (include/scone_hip.h, "lean optimizer step"): plain SGD or row-wise Adagrad -- ONE fp32 accumulator per
+// row -- on an fp32 master row (master mode: the served row is re-stored in the table's format, as k_opt_step does) or on the
+// served fp32 / bf16 row itself (in-place mode: no master copy; bf16 rows rounded to nearest or stochastically).
+//
+// Shape.  k_opt_step's: one wave per listed row, a grid-stride loop over the list, lane l owns the 16-byte pieces l, l + 64, ..
+// of g (and the 8-byte pieces of a bf16 row: the same elements), blocks of OPT_NT * 64 pieces with the loads of a block issued
+// before its arithmetic.  Row-wise Adagrad needs q, the row's sum of g1 * g1, before the first update: a row of up to 1024
+// elements is one block whose g stays in registers; a wider row walks g twice (the second walk re-reads what this wave has just
+// read).  Either way a lane adds its elements in ascending j, so block boundaries cannot change a bit; the lanes are combined by
+// the butterfly the contract states.  The row's accumulator is read and written by lane 0; s' reaches the other lanes by a shuffle.
+//
+// Arithmetic.  Every operation is one IEEE fp32 rounding: built with -ffp-contract=off, nothing here calls fmaf, sqrtf and / are
+// hipcc's correctly rounded defaults and subnormals are kept (tests/test_gpu_opt_lean.py pins all of it).  The stores of every
+// row format are scone_opt_rows.h's, shared with k_opt_step.  Plain vector stores only; the one atomic is the integer atomicOr
+// on the status word.
+#include "scone_common.h"
+#include "scone_opt_rows.h"
+#include "scone_quant.h"
+
+#include <cmath>
+
+namespace {
+
+struct lean_rand {
+  uint64_t seed;
+  int64_t step;
+};
+
+__device__ __forceinline__ float lean_scale(const scone_opt_scalars &k, float g) { return k.gscale == 1.0f ? g : g * k.gscale; }
+
+__device__ __forceinline__ void lean_scale4(const scone_opt_scalars &k, float4 &g) {
+  g.x = lean_scale(k, g.x), g.y = lean_scale(k, g.y), g.z = lean_scale(k, g.z), g.w = lean_scale(k, g.w);
+}
+
+// a lane's part of q: its elements in ascending j, the product rounded first, then the sum.  A piece the lane does not have is
+// all +0.0f: q + (+0.0f * +0.0f) keeps every bit of q (q is never -0.0f: it starts at +0.0f and only squares are added)
+__device__ __forceinline__ float lean_sum_sq(float q, const float4 &g1) {
+  const float a = g1.x * g1.x, b = g1.y * g1.y, c = g1.z * g1.z, e = g1.w * g1.w;
+  q = q + a;
+  q = q + b;
+  q = q + c;
+  q = q + e;
+  return q;
+}
+
+// one element from g1 (already scaled): the contract's statement, one rounding per operation
+template <int KIND>
+__device__ __forceinline__ float lean_elem(const scone_opt_scalars &k, float g1, float w, float den) {
+  float w1 = w;
+  if (k.decay != 0.0f) {
+    const float dw = k.decay * w;
+    w1 = w - dw;
+  }
+  const float num = k.alpha * g1;
+  if (KIND == SCONE_LEAN_SGD) return w1 - num;
+  return w1 - num / den;
+}
+
+// SCONE_ROUND_STOCHASTIC of one element: (u + r) >> 16, r = 16 random bits; an inf / NaN is rounded as nearest does
+__device__ __forceinline__ uint32_t lean_bf16_stochastic(float x, uint32_t row_key, uint32_t col) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7F800000u) == 0x7F800000u) return scone_f32_to_bf16_bits(x);
+  return (u + scone_lean_rand16_of(row_key, col)) >> 16;
+}
+
+template <int FMT, int KIND, bool INPLACE, bool STOCH>
+__global__ __launch_bounds__(256) void k_opt_lean(const int64_t *__restrict__ ids, const float *__restrict__ grad,
+                                                  unsigned long long n, unsigned long long row_begin, unsigned long long row_end,
+                                                  int d, scone_opt_scalars sc, lean_rand rnd, float *__restrict__ master,
+                                                  float *__restrict__ row_state, scone_row_store st, __half *__restrict__ scales,
+                                                  uint32_t *__restrict__ status) {
+  static_assert(!INPLACE || FMT == SCONE_FMT_F32 || FMT == SCONE_FMT_BF16, "only fp32 and bf16 rows are weights in place");
+  static_assert(!STOCH || (INPLACE && FMT == SCONE_FMT_BF16), "only an in-place bf16 row is rounded");
+  constexpr bool ROWWISE = KIND == SCONE_LEAN_ROWWISE_ADAGRAD;
+  const int lane = threadIdx.x & 63;
+  const int pieces = d >> 2;
+  const bool one_block = pieces <= OPT_NT * 64;
+  const unsigned long long nwaves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+  for (unsigned long long r = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < n; r += nwaves) {
+    const long long id = ids[r];
+    // wave-uniform: outside the owned range, or not above its predecessor in the list -> skipped, never an address
+    if ((unsigned long long)id < row_begin || (unsigned long long)id >= row_end || (r > 0 && id <= ids[r - 1])) {
+      if (lane == 0) atomicOr(status, SCONE_ST_BAD_ID);
+      continue;
+    }
+    const unsigned long long lr = (unsigned long long)id - row_begin;
+    const float4 *G = reinterpret_cast<const float4 *>(grad + r * (unsigned long long)d);
+    // the weights: the master row, or the served row itself
+    float4 *W = INPLACE ? reinterpret_cast<float4 *>(st.row(lr)) : reinterpret_cast<float4 *>(master + lr * (unsigned long long)d);
+    uint2 *W16 = reinterpret_cast<uint2 *>(st.row(lr));  // an in-place bf16 row: piece p is 8 bytes
+    const uint32_t row_key = STOCH ? scone_lean_row_key(rnd.seed, rnd.step, (uint64_t)id) : 0u;
+
+    float4 g[OPT_NT], w[OPT_NT];
+    bool on[OPT_NT];
+    auto load_block = [&](int p0) {  // both streams of a block in flight before any arithmetic
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) {
+        const int p = p0 + t * 64 + lane;
+        on[t] = p < pieces;
+        g[t] = w[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (on[t]) {
+          g[t] = G[p];
+          if (INPLACE && FMT == SCONE_FMT_BF16) {
+            const uint2 b = W16[p];
+            w[t] = make_float4(__uint_as_float(b.x << 16), __uint_as_float(b.x & 0xFFFF0000u), __uint_as_float(b.y << 16),
+                               __uint_as_float(b.y & 0xFFFF0000u));
+          } else {
+            w[t] = W[p];
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) lean_scale4(sc, g[t]);
+    };
+
+    float den = 0.f;
+    if (ROWWISE) {
+      float q = 0.f;
+      if (one_block) {
+        load_block(0);
+#pragma unroll
+        for (int t = 0; t < OPT_NT; ++t) q = lean_sum_sq(q, g[t]);
+      } else {
+        for (int p0 = 0; p0 < pieces; p0 += OPT_NT * 64) {
+          float4 x[OPT_NT];
+#pragma unroll
+          for (int t = 0; t < OPT_NT; ++t) {
+            const int p = p0 + t * 64 + lane;
+            x[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p < pieces) x[t] = G[p];
+          }
+#pragma unroll
+          for (int t = 0; t < OPT_NT; ++t) {
+            lean_scale4(sc, x[t]);
+            q = lean_sum_sq(q, x[t]);
+          }
+        }
+      }
+      for (int s = 32; s >= 1; s >>= 1) q = q + __shfl_xor(q, s, 64);  // the contract's butterfly: every lane ends with the same bits
+      float s_new = 0.f;
+      if (lane == 0) {
+        const float g2 = q / (float)d;
+        s_new = row_state[lr] + g2;
+        row_state[lr] = s_new;
+      }
+      s_new = __shfl(s_new, 0, 64);
+      den = sqrtf(s_new) + sc.eps;
+    }
+
+    float rowmax = 0.f;  // INT8 only
+    for (int p0 = 0; p0 < pieces; p0 += OPT_NT * 64) {
+      if (!(ROWWISE && one_block)) load_block(p0);
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) {
+        w[t].x = lean_elem<KIND>(sc, g[t].x, w[t].x, den);
+        w[t].y = lean_elem<KIND>(sc, g[t].y, w[t].y, den);
+        w[t].z = lean_elem<KIND>(sc, g[t].z, w[t].z, den);
+        w[t].w = lean_elem<KIND>(sc, g[t].w, w[t].w, den);
+      }
+#pragma unroll
+      for (int t = 0; t < OPT_NT; ++t) {
+        const int p = p0 + t * 64 + lane;
+        if (!INPLACE && on[t]) W[p] = w[t];
+        if (STOCH) {
+          const uint32_t j = (uint32_t)p << 2;
+          if (on[t])
+            W16[p] = make_uint2(lean_bf16_stochastic(w[t].x, row_key, j) | (lean_bf16_stochastic(w[t].y, row_key, j + 1) << 16),
+                                lean_bf16_stochastic(w[t].z, row_key, j + 2) | (lean_bf16_stochastic(w[t].w, row_key, j + 3) << 16));
+        } else if (FMT == SCONE_FMT_I8) {
+          if (on[t]) rowmax = opt_i8_amax(rowmax, w[t]);
+        } else if (p0 + t * 64 < pieces) {  // wave-uniform: a pass with no piece at all has no shuffles either
+          opt_store_piece<FMT>(st, scales, lr, d, p, on[t], w[t], lane);
+        }
+      }
+      if (FMT == SCONE_FMT_I8 && one_block) opt_i8_store_block(st, scales, lr, p0, lane, on, w, rowmax);
+    }
+    if (FMT == SCONE_FMT_I8 && !one_block) opt_i8_store_wide(st, scales, lr, W, pieces, lane, rowmax);
+  }
+}
+
+const char *lean_check(const scone_lean_cfg *cfg) {
+  if (!cfg) return "null cfg";
+  if (cfg->struct_size != sizeof(scone_lean_cfg)) return "cfg.struct_size does not match this library";
+  if (cfg->kind != SCONE_LEAN_SGD && cfg->kind != SCONE_LEAN_ROWWISE_ADAGRAD) return "bad kind";
+  if (cfg->rounding != SCONE_ROUND_NEAREST && cfg->rounding != SCONE_ROUND_STOCHASTIC) return "bad rounding";
+  if (cfg->reserved != 0) return "cfg.reserved must be 0";
+  if (!std::isfinite(cfg->lr) || !std::isfinite(cfg->eps) || !std::isfinite(cfg->weight_decay) || !std::isfinite(cfg->grad_scale))
+    return "lr, eps, weight_decay and grad_scale must be finite";
+  return nullptr;
+}
+
+void lean_scalars(const scone_lean_cfg *cfg, scone_opt_scalars *out) {
+  *out = scone_opt_scalars{};
+  out->alpha = (float)cfg->lr;
+  out->eps = (float)cfg->eps;
+  out->decay = (float)(cfg->lr * cfg->weight_decay);
+  out->gscale = (float)cfg->grad_scale;
+}
+
+const char *fmt_name(int fmt) {
+  switch (fmt) {
+    case SCONE_FMT_F32: return "fp32";
+    case SCONE_FMT_F16: return "fp16";
+    case SCONE_FMT_I8: return "int8";
+    case SCONE_FMT_I4: return "int4";
+    case SCONE_FMT_BF16: return "bf16";
+    case SCONE_FMT_MXFP4: return "mxfp4";
+    default: return "unknown";
+  }
+}
+
+struct lean_args {
+  const int64_t *ids;
+  const float *grad;
+  unsigned long long n;
+  scone_opt_scalars sc;
+  lean_rand rnd;
+  float *master, *row_state;
+};
+
+template <int FMT, int KIND, bool INPLACE, bool STOCH>
+void lean_launch(scone_handle *h, const lean_args &a, unsigned blocks, hipStream_t s) {
+  hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, a.n,
+                     (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.rnd, a.master,
+                     a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status);
+}
+
+template <int FMT, bool INPLACE, bool STOCH>
+void lean_launch_kind(scone_handle *h, int kind, const lean_args &a, unsigned blocks, hipStream_t s) {
+  if (kind == SCONE_LEAN_SGD)
+    lean_launch<FMT, SCONE_LEAN_SGD, INPLACE, STOCH>(h, a, blocks, s);
+  else
+    lean_launch<FMT, SCONE_LEAN_ROWWISE_ADAGRAD, INPLACE, STOCH>(h, a, blocks, s);
+}
+
+}  // namespace
+
+extern "C" int scone_lean_scalars_of(const scone_lean_cfg *cfg, scone_opt_scalars *out) {
+  if (!out || lean_check(cfg)) return SCONE_EINVAL;
+  lean_scalars(cfg, out);
+  return SCONE_OK;
+}
+
+extern "C" uint32_t scone_lean_rand16(uint64_t seed, int64_t step, uint64_t row_id, uint32_t col) {
+  return scone_lean_rand16_of(scone_lean_row_key(seed, step, row_id), col);
+}
+
+extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                                   uint64_t n, float *d_master, float *d_row_state, scone_stream_t stream) {
+  if (!h) return SCONE_EINVAL;
+  if (const char *bad = lean_check(cfg)) return scone_fail(h, SCONE_EINVAL, (std::string("scone_opt_step_lean: ") + bad).c_str());
+  if (h->cfg.dim == 0) return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: handle has no table (dim == 0)");
+  if (!h->rows) return scone_fail(h, SCONE_ESTATE, "scone_opt_step_lean: handle has no table");
+  const int fmt = h->cfg.table_fmt;
+  const bool inplace = d_master == nullptr, stoch = cfg->rounding == SCONE_ROUND_STOCHASTIC;
+  if (inplace && fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
+    return scone_fail(h, SCONE_EINVAL,
+                      (std::string("scone_opt_step_lean: in place (d_master == NULL) needs an fp32 or bf16 table, this one is ") +
+                       fmt_name(fmt)).c_str());
+  if (stoch && !inplace)
+    return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: stochastic rounding with a master: there is nothing to round");
+  if (stoch && fmt != SCONE_FMT_BF16)
+    return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: stochastic rounding on an fp32 table: there is nothing to round");
+  if (n == 0) return SCONE_OK;
+  if (!d_row_ids || !d_grad_rows) return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: null pointer");
+  if (cfg->kind == SCONE_LEAN_ROWWISE_ADAGRAD && !d_row_state)
+    return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: row-wise Adagrad needs d_row_state (one fp32 per owned row)");
+  SCONE_ON_DEVICE(h);
+  if (h->stage) scone_stage_destroy(h);  // the table changes: as scone_opt_step (the staged cache of cold rows is dropped)
+  lean_args a;
+  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state;
+  a.rnd.seed = cfg->seed, a.rnd.step = cfg->step;
+  lean_scalars(cfg, &a.sc);
+  unsigned blocks = scone_capped_blocks((n + 3) / 4);
+  if (h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks) blocks = (unsigned)h->opt_max_blocks;
+  hipStream_t s = (hipStream_t)stream;
+  if (inplace) {
+    if (fmt == SCONE_FMT_F32)
+      lean_launch_kind<SCONE_FMT_F32, true, false>(h, cfg->kind, a, blocks, s);
+    else if (stoch)
+      lean_launch_kind<SCONE_FMT_BF16, true, true>(h, cfg->kind, a, blocks, s);
+    else
+      lean_launch_kind<SCONE_FMT_BF16, true, false>(h, cfg->kind, a, blocks, s);
+  } else {
+    switch (fmt) {
+      case SCONE_FMT_F32: lean_launch_kind<SCONE_FMT_F32, false, false>(h, cfg->kind, a, blocks, s); break;
+      case SCONE_FMT_F16: lean_launch_kind<SCONE_FMT_F16, false, false>(h, cfg->kind, a, blocks, s); break;
+      case SCONE_FMT_I8: lean_launch_kind<SCONE_FMT_I8, false, false>(h, cfg->kind, a, blocks, s); break;
+      case SCONE_FMT_I4: lean_launch_kind<SCONE_FMT_I4, false, false>(h, cfg->kind, a, blocks, s); break;
+      case SCONE_FMT_BF16: lean_launch_kind<SCONE_FMT_BF16, false, false>(h, cfg->kind, a, blocks, s); break;
+      case SCONE_FMT_MXFP4: lean_launch_kind<SCONE_FMT_MXFP4, false, false>(h, cfg->kind, a, blocks, s); break;
+      default: return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: bad format");
+    }
+  }
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}

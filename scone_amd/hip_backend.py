@@ -347,6 +347,42 @@ def opt_scalars(kind, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_s
     return {name: np.float32(getattr(out, name)) for name, _ in L.OptScalars._fields_}
 
 
+_LEAN = {"sgd": L.LEAN_SGD, "rowwise_adagrad": L.LEAN_ROWWISE_ADAGRAD}
+_ROUND = {"nearest": L.ROUND_NEAREST, "stochastic": L.ROUND_STOCHASTIC}
+
+
+def _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step) -> "L.LeanCfg":
+    if isinstance(kind, str):
+        if kind.lower() not in _LEAN:
+            raise ValueError(f"unknown lean optimizer kind {kind!r} (sgd, rowwise_adagrad)")
+        kind = _LEAN[kind.lower()]
+    if isinstance(rounding, str):
+        if rounding.lower() not in _ROUND:
+            raise ValueError(f"unknown rounding {rounding!r} (nearest, stochastic)")
+        rounding = _ROUND[rounding.lower()]
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must fit 64 unsigned bits")
+    return L.LeanCfg(C.sizeof(L.LeanCfg), int(kind), int(rounding), 0, float(lr), float(eps), float(weight_decay), float(grad_scale),
+                     int(seed), int(step))
+
+
+def lean_scalars(kind, lr, eps=1e-10, weight_decay=0.0, grad_scale=1.0) -> dict:
+    """``scone_lean_scalars_of``: the fp32 scalars ``scone_opt_step_lean`` computes with (``alpha = lr``, ``eps``, ``decay = lr *
+    weight_decay``, ``gscale``; the other fields of ``scone_opt_scalars`` are 0), each an ``np.float32``.  Runs without a GPU;
+    ``ValueError`` for what the library refuses."""
+    out = L.OptScalars()
+    rc = L.lib().scone_lean_scalars_of(C.byref(_lean_cfg(kind, lr, eps, weight_decay, grad_scale, "nearest", 0, 1)), C.byref(out))
+    if rc != L.OK:
+        _raise(rc, "scone_lean_scalars_of: bad kind or a hyper-parameter that is not finite")
+    return {name: np.float32(getattr(out, name)) for name, _ in L.OptScalars._fields_}
+
+
+def lean_rand16(seed: int, step: int, row_id: int, col: int) -> int:
+    """``scone_lean_rand16``: the 16 random bits of stochastic rounding for element ``col`` of GLOBAL row ``row_id`` (the host
+    copy of the device function).  Runs without a GPU."""
+    return int(L.lib().scone_lean_rand16(int(seed), int(step), int(row_id), int(col)))
+
+
 class BackwardPlan:
     """``scone_bwd_plan``: the sorted reference stream of one batch on one :class:`SconeTable` (include/scone_hip.h,
     "backward").  ``n_rows`` distinct rows have at least one of the ``n_refs`` references.  :meth:`rows` may be called any
@@ -988,6 +1024,49 @@ class SconeTable:
             rc = L.lib().scone_opt_step(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
                                         _ptr(state1), _ptr(state2), stream.cuda_stream)
         self._check(rc, "scone_opt_step")
+        if row_ids.numel():                                        # they may be temporaries of the caller
+            row_ids.record_stream(stream)
+            grad_rows.record_stream(stream)
+
+    def opt_step_lean(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, *, kind, lr: float, master: Optional[torch.Tensor] = None,
+                      row_state: Optional[torch.Tensor] = None, eps: float = 1e-10, weight_decay: float = 0.0,
+                      grad_scale: float = 1.0, rounding="nearest", seed: int = 0, step: int = 1) -> None:
+        """``scone_opt_step_lean``: the lean optimizer step (include/scone_hip.h, "lean optimizer step").  ``kind``: ``"sgd"`` or
+        ``"rowwise_adagrad"`` (ONE fp32 accumulator per row: ``row_state``, fp32 ``[row_end - row_begin]``, contiguous, on the
+        table's device, updated in place).  ``master`` given (fp32 ``[row_end - row_begin, d]``): it is updated in place and
+        the served rows are re-stored in the table's format, as :meth:`opt_step` does.  ``master=None``: IN PLACE -- the served
+        fp32 / bf16 rows are the weights; bf16 rows are rounded to ``"nearest"`` or ``"stochastic"`` (random bits keyed by
+        ``seed``, ``step``, the global row id and the column).  One kernel launch on the current stream; no synchronisation."""
+        cfg = _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step)
+        owned = self.row_end - self.row_begin
+        if master is None and self.fmt not in (L.FMT_F32, L.FMT_BF16):
+            raise ValueError("opt_step_lean: in place (master=None) needs an fp32 or bf16 table, this one has format code "
+                             f"{self.fmt}")
+        if cfg.rounding == L.ROUND_STOCHASTIC and (master is not None or self.fmt != L.FMT_BF16):
+            raise ValueError("opt_step_lean: stochastic rounding is for in-place bf16 rows (with a master or on an fp32 table "
+                             "there is nothing to round)")
+        for name, t, shape, needed in (("master", master, (owned, self.dim), False),
+                                       ("row_state", row_state, (owned,), cfg.kind == L.LEAN_ROWWISE_ADAGRAD)):
+            if t is None:
+                if needed:
+                    raise ValueError(f"opt_step_lean: this kind needs {name}")
+                continue
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape
+                    and t.device == self.device and t.is_contiguous()):
+                raise ValueError(f"opt_step_lean: {name} must be a contiguous fp32 {list(shape)} tensor on {self.device} "
+                                 "(it is updated in place)")
+        if row_ids.dim() != 1 or grad_rows.dim() != 2 or grad_rows.shape[0] != row_ids.numel() or grad_rows.shape[1] != self.dim:
+            raise ValueError(f"opt_step_lean: row_ids [U] and grad_rows [U, {self.dim}], got {tuple(row_ids.shape)} and "
+                             f"{tuple(grad_rows.shape)}")
+        if row_ids.dtype != torch.int64 or grad_rows.dtype != torch.float32:
+            raise ValueError("opt_step_lean: row_ids must be int64 and grad_rows fp32")
+        row_ids = row_ids.to(device=self.device).contiguous()
+        grad_rows = grad_rows.to(device=self.device).contiguous()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_opt_step_lean(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
+                                             _ptr(row_state), stream.cuda_stream)
+        self._check(rc, "scone_opt_step_lean")
         if row_ids.numel():                                        # they may be temporaries of the caller
             row_ids.record_stream(stream)
             grad_rows.record_stream(stream)

@@ -15,6 +15,7 @@ from typing import Optional
 import torch
 from torch import nn
 
+from scone_amd import _lib
 from scone_amd.inference.embedding_cache import EmbeddingCache
 
 
@@ -70,11 +71,8 @@ class _Lookup(torch.autograd.Function):
         with table.backward_plan(ctx.tok, ctx.cu) as plan:
             if ctx.needs_input_grad[0]:
                 row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
-                module._touched.append(row_ids)
-                # set here, not returned: autograd's accumulation re-creates a sparse gradient without its coalesced flag
-                sparse = torch.sparse_coo_tensor(row_ids[None], grad_rows, tuple(module.weight.shape), is_coalesced=True)
-                weight = module.weight
-                weight.grad = sparse if weight.grad is None else _add_coalesced(weight.grad, row_ids, grad_rows)
+                # set on the module, not returned: autograd's accumulation re-creates a sparse gradient without its coalesced flag
+                module._accumulate(row_ids, grad_rows)
             if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
                 grad_base = grad_out
                 if module.cache.lookup_mode == "longest_suffix":     # a matched f-gram replaced the base row
@@ -116,6 +114,12 @@ class TrainableFGramTable(nn.Module):
                 out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         return _Lookup.apply(self.weight, base, self, input_ids, cu_seqlens, reduce, out_dtype)
 
+    def _accumulate(self, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        self._touched.append(row_ids)
+        sparse = torch.sparse_coo_tensor(row_ids[None], grad_rows, tuple(self.weight.shape), is_coalesced=True)
+        weight = self.weight
+        weight.grad = sparse if weight.grad is None else _add_coalesced(weight.grad, row_ids, grad_rows)
+
     @torch.no_grad()
     def commit(self, ids: Optional[torch.Tensor] = None) -> int:
         """Re-store ``weight[ids]`` into the served table (``ids=None``: the rows touched by a backward since the last
@@ -131,6 +135,34 @@ class TrainableFGramTable(nn.Module):
         return int(ids.numel())
 
 
+class InPlaceFGramTable(nn.Module):
+    """The f-gram table of ``cache`` trained IN PLACE: the served fp32 / bf16 rows are the weights, and there is no ``[N, d]``
+    tensor of any kind (include/scone_hip.h, "lean optimizer step").  ``forward`` and ``grad_base`` are
+    :class:`TrainableFGramTable`'s.  ``anchor``, a parameter of zero elements, only makes autograd call the backward; the
+    sparse gradient lands on the module as ``grad = (row_ids, grad_rows)`` -- ``row_ids`` int64 ``[U]`` sorted and distinct,
+    ``grad_rows`` fp32 ``[U, d]`` -- and a backward onto a gradient that is already there adds to it (a row both have is one fp32
+    add, a row one has is that row, bit for bit).  Only :class:`FGramOptimizer` (``"sgd"`` or ``"rowwise_adagrad"``) updates it."""
+
+    def __init__(self, cache: EmbeddingCache) -> None:
+        super().__init__()
+        table = cache.to_device()
+        self.cache = cache
+        self.shape = (table.n_rows, table.dim)
+        self.anchor = nn.Parameter(torch.zeros(0, dtype=torch.float32, device=table.device))
+        self.grad = None
+
+    def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
+                out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        return _Lookup.apply(self.anchor, base, self, input_ids, cu_seqlens, reduce, out_dtype)
+
+    def _accumulate(self, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        if self.grad is not None:
+            old = torch.sparse_coo_tensor(self.grad[0][None], self.grad[1], self.shape, is_coalesced=True)
+            both = _add_coalesced(old, row_ids, grad_rows)
+            row_ids, grad_rows = both._indices()[0], both._values()
+        self.grad = (row_ids, grad_rows)
+
+
 class FGramOptimizer:
     """The fused sparse optimizer of a :class:`TrainableFGramTable` (include/scone_hip.h, "optimizer step").
 
@@ -140,19 +172,46 @@ class FGramOptimizer:
     arithmetic of ``torch.optim.SparseAdam``: lazy moments, bias correction folded into the step size); ``weight_decay`` is
     decoupled and lazy (only the touched rows decay).  Adam's ``m`` / ``v`` and Adagrad's sum of squares are fp32 ``[N, d]``
     on the table's device, allocated at the first step.  ``lr`` is a plain attribute: change it between steps (schedules are
-    the caller's).  No host synchronisation, no ``coalesce()``; the same bits on every run."""
+    the caller's).  No host synchronisation, no ``coalesce()``; the same bits on every run.
 
-    def __init__(self, module: TrainableFGramTable, kind: str = "adam", lr: float = 1e-3, betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0) -> None:
-        if kind not in ("sgd", "adagrad", "adam"):
-            raise ValueError(f"unknown optimizer kind {kind!r} (sgd, adagrad, adam)")
+    The lean kinds (include/scone_hip.h, "lean optimizer step").  ``"rowwise_adagrad"`` keeps ONE fp32 accumulator per row:
+    ``state2`` is fp32 ``[N]``.  On a :class:`TrainableFGramTable` it updates the fp32 master and re-stores the served rows, as
+    the other kinds do.  On an :class:`InPlaceFGramTable` (``"sgd"`` or ``"rowwise_adagrad"`` only, an fp32 or bf16 cache only)
+    the served rows themselves are updated; ``rounding="stochastic"`` (bf16 rows) draws its bits from ``seed``, the step count
+    ``t``, the row id and the column, so a run is reproducible and a resumed one (``state_dict``) continues it."""
+
+    def __init__(self, module, kind: str = "adam", lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, rounding: str = "nearest", seed: int = 0) -> None:
+        self.in_place = isinstance(module, InPlaceFGramTable)
+        kinds = ("sgd", "rowwise_adagrad") if self.in_place else ("sgd", "adagrad", "adam", "rowwise_adagrad")
+        if kind not in kinds:
+            raise ValueError(f"unknown optimizer kind {kind!r} for a {type(module).__name__} ({', '.join(kinds)})")
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"unknown rounding {rounding!r} (nearest, stochastic)")
+        if self.in_place:
+            fmt = module.cache.to_device().fmt
+            if fmt not in (_lib.FMT_F32, _lib.FMT_BF16):
+                raise ValueError("an InPlaceFGramTable is trained on an fp32 or bf16 cache: a quantised or fp16 row cannot hold "
+                                 "small updates")
+            if rounding == "stochastic" and fmt != _lib.FMT_BF16:
+                raise ValueError("stochastic rounding is for bf16 rows: an fp32 row has nothing to round")
+        elif rounding == "stochastic":
+            raise ValueError("stochastic rounding is for an InPlaceFGramTable: a master copy has nothing to round")
         self.module, self.kind = module, kind
+        self.rounding, self.seed = rounding, int(seed)
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.t = 0
         self.state1: Optional[torch.Tensor] = None     # Adam's m
         self.state2: Optional[torch.Tensor] = None     # Adam's v / Adagrad's sum of squares
 
     def _ensure_state(self) -> None:
+        if self.kind == "rowwise_adagrad":
+            if self.state2 is None:
+                table = self.module.cache.to_device()
+                self.state2 = torch.zeros(table.n_rows, dtype=torch.float32, device=table.device)
+            return
+        if self.in_place:
+            return
         w = self.module.weight
         if self.kind == "adam" and self.state1 is None:
             self.state1 = torch.zeros_like(w.detach(), memory_format=torch.contiguous_format)
@@ -164,6 +223,8 @@ class FGramOptimizer:
         """One update from ``module.weight.grad`` (``None``: nothing happens, ``t`` stays).  ``grad_scale`` multiplies the
         gradient first (an un-scaling of a loss scale, a 1 / accumulation count).  Returns the number of rows updated."""
         module = self.module
+        if self.in_place:
+            return self._step_in_place(grad_scale)
         weight, grad = module.weight, module.weight.grad
         if grad is None:
             return 0
@@ -181,13 +242,39 @@ class FGramOptimizer:
         def own(x):                                      # the rows this handle owns: a contiguous view
             return None if x is None else x[lo:hi]
 
-        table.opt_step(row_ids, grad_rows, own(weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
-                       state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
-                       grad_scale=grad_scale)
+        if self.kind == "rowwise_adagrad":
+            table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, master=own(weight.detach()),
+                                row_state=own(self.state2), eps=self.eps, weight_decay=self.weight_decay, grad_scale=grad_scale,
+                                step=self.t)
+        else:
+            table.opt_step(row_ids, grad_rows, own(weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
+                           state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                           grad_scale=grad_scale)
         module._touched = []                             # the served table is current: commit() has nothing to store
         return int(row_ids.numel())
 
+    def _step_in_place(self, grad_scale: float) -> int:
+        module = self.module
+        if module.grad is None:
+            return 0
+        row_ids, grad_rows = module.grad
+        table = module.cache.to_device()
+        self.t += 1
+        self._ensure_state()
+        state = None if self.state2 is None else self.state2[table.row_begin:table.row_end]
+        table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, row_state=state, eps=self.eps,
+                            weight_decay=self.weight_decay, grad_scale=grad_scale, rounding=self.rounding, seed=self.seed, step=self.t)
+        return int(row_ids.numel())
+
     def zero_grad(self, set_to_none: bool = True) -> None:
+        if self.in_place:
+            module = self.module
+            if module.grad is not None and not set_to_none:
+                ids, rows = module.grad
+                module.grad = (ids[:0], rows[:0])
+            else:
+                module.grad = None
+            return
         grad = self.module.weight.grad
         if grad is None:
             return
@@ -201,7 +288,7 @@ class FGramOptimizer:
 
     def state_dict(self) -> dict:
         return {"kind": self.kind, "t": self.t, "lr": self.lr, "betas": self.betas, "eps": self.eps,
-                "weight_decay": self.weight_decay,
+                "weight_decay": self.weight_decay, "rounding": self.rounding, "seed": self.seed,
                 "state1": None if self.state1 is None else self.state1.clone(),
                 "state2": None if self.state2 is None else self.state2.clone()}
 
@@ -210,11 +297,16 @@ class FGramOptimizer:
             raise ValueError(f"state of a {state['kind']!r} optimizer loaded into a {self.kind!r} one")
         self.t, self.lr, self.eps, self.weight_decay = int(state["t"]), float(state["lr"]), float(state["eps"]), float(state["weight_decay"])
         self.betas = (float(state["betas"][0]), float(state["betas"][1]))
-        w = self.module.weight
+        rounding = state.get("rounding", "nearest")
+        if rounding == "stochastic" and not (self.in_place and self.module.cache.to_device().fmt == _lib.FMT_BF16):
+            raise ValueError("a state with stochastic rounding is for an InPlaceFGramTable on a bf16 cache")
+        self.rounding, self.seed = rounding, int(state.get("seed", 0))
+        table = self.module.cache.to_device()
+        shape = (table.n_rows,) if self.kind == "rowwise_adagrad" else (table.n_rows, table.dim)
         for name in ("state1", "state2"):
             s = state[name]
             if s is not None:
-                if tuple(s.shape) != tuple(w.shape):
-                    raise ValueError(f"{name} must be [{w.shape[0]}, {w.shape[1]}], got {tuple(s.shape)}")
-                s = s.to(device=w.device, dtype=torch.float32).contiguous().clone()
+                if tuple(s.shape) != shape:
+                    raise ValueError(f"{name} must be {list(shape)}, got {list(s.shape)}")
+                s = s.to(device=table.device, dtype=torch.float32).contiguous().clone()
             setattr(self, name, s)
