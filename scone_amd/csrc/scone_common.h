@@ -10,6 +10,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/scone_hip.h"
@@ -230,6 +231,42 @@ struct scone_handle {
 
 int scone_fail(scone_handle *h, int code, const char *what);
 int scone_hip_fail(scone_handle *h, hipError_t e, const char *what);
+// A refusal in the name of entry point `who`: "<who>: <what>".  The text is built here, on the failure path only.
+__attribute__((cold, minsize)) static inline int scone_refuse(scone_handle *h, int code, const char *who, const char *what) {
+  return scone_fail(h, code, (std::string(who) + ": " + what).c_str());
+}
+// every entry point that reads or writes table rows starts with this
+static inline int scone_need_table(scone_handle *h, const char *who) {
+  if (!h) return SCONE_EINVAL;
+  if (h->cfg.dim <= 0 || !h->rows) return scone_refuse(h, SCONE_ESTATE, who, "handle has no table (dim == 0)");
+  return SCONE_OK;
+}
+static inline size_t scone_dt_bytes(int out_dtype) { return out_dtype == SCONE_DT_F32 ? 4 : 2; }  // a valid SCONE_DT_*
+
+// table_fmt as a compile-time constant: f(std::integral_constant<int, SCONE_FMT_*>()); -1 for an unknown format (host code)
+template <typename F>
+static int scone_dispatch_fmt(int fmt, F &&f) {
+  switch (fmt) {
+    case SCONE_FMT_F32: f(std::integral_constant<int, SCONE_FMT_F32>()); return 0;
+    case SCONE_FMT_F16: f(std::integral_constant<int, SCONE_FMT_F16>()); return 0;
+    case SCONE_FMT_I8: f(std::integral_constant<int, SCONE_FMT_I8>()); return 0;
+    case SCONE_FMT_I4: f(std::integral_constant<int, SCONE_FMT_I4>()); return 0;
+    case SCONE_FMT_BF16: f(std::integral_constant<int, SCONE_FMT_BF16>()); return 0;
+    case SCONE_FMT_MXFP4: f(std::integral_constant<int, SCONE_FMT_MXFP4>()); return 0;
+    default: return -1;
+  }
+}
+static inline const char *scone_fmt_name(int fmt) {
+  switch (fmt) {
+    case SCONE_FMT_F32: return "fp32";
+    case SCONE_FMT_F16: return "fp16";
+    case SCONE_FMT_I8: return "int8";
+    case SCONE_FMT_I4: return "int4";
+    case SCONE_FMT_BF16: return "bf16";
+    case SCONE_FMT_MXFP4: return "mxfp4";
+    default: return "unknown";
+  }
+}
 scone_row_store scone_store_of(const scone_handle *h);
 struct scone_index_view;
 void scone_index_view_of(const scone_handle *h, scone_index_view *v);  // scone_index.hip
@@ -294,6 +331,13 @@ struct scone_device_guard {
   do {                                                           \
     hipError_t e__ = (call);                                     \
     if (e__ != hipSuccess) return scone_hip_fail((h), e__, #call); \
+  } while (0)
+
+// a step whose non-zero status is the caller's
+#define SCONE_TRY(call)          \
+  do {                           \
+    const int rc__ = (call);     \
+    if (rc__) return rc__;       \
   } while (0)
 
 // launchers implemented in the kernel translation units

@@ -181,32 +181,19 @@ extern "C" int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars 
 
 extern "C" int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
                               float *d_master, float *d_state1, float *d_state2, scone_stream_t stream) {
-  if (!h) return SCONE_EINVAL;
-  if (const char *bad = opt_check(cfg)) return scone_fail(h, SCONE_EINVAL, (std::string("scone_opt_step: ") + bad).c_str());
-  if (h->cfg.dim == 0) return scone_fail(h, SCONE_EINVAL, "scone_opt_step: handle has no table (dim == 0)");
-  if (!h->rows) return scone_fail(h, SCONE_ESTATE, "scone_opt_step: handle has no table");
+  const char *who = "scone_opt_step";
+  SCONE_TRY(opt_need_table(h, who, opt_check(cfg)));
   if (n == 0) return SCONE_OK;
-  if (!d_row_ids || !d_grad_rows || !d_master) return scone_fail(h, SCONE_EINVAL, "scone_opt_step: null pointer");
-  if (cfg->kind == SCONE_OPT_ADAM && !d_state1) return scone_fail(h, SCONE_EINVAL, "scone_opt_step: Adam needs d_state1 (m)");
-  if (cfg->kind != SCONE_OPT_SGD && !d_state2)
-    return scone_fail(h, SCONE_EINVAL, "scone_opt_step: Adam / Adagrad need d_state2 (v / the sum of squares)");
+  if (!d_row_ids || !d_grad_rows || !d_master) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
+  if (cfg->kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, who, "Adam needs d_state1 (m)");
+  if (cfg->kind != SCONE_OPT_SGD && !d_state2) return scone_refuse(h, SCONE_EINVAL, who, "Adam / Adagrad need d_state2 (v / the sum of squares)");
   SCONE_ON_DEVICE(h);
-  if (h->stage) scone_stage_destroy(h);  // the table changes: as scone_table_store_f32_ids (the staged cache of cold rows is dropped)
   opt_args a;
   a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2;
   opt_scalars(cfg, &a.sc);
-  unsigned blocks = scone_capped_blocks((n + 3) / 4);
-  if (h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks) blocks = (unsigned)h->opt_max_blocks;
-  hipStream_t s = (hipStream_t)stream;
-  switch (h->cfg.table_fmt) {
-    case SCONE_FMT_F32: opt_launch_kind<SCONE_FMT_F32>(h, cfg->kind, a, blocks, s); break;
-    case SCONE_FMT_F16: opt_launch_kind<SCONE_FMT_F16>(h, cfg->kind, a, blocks, s); break;
-    case SCONE_FMT_I8: opt_launch_kind<SCONE_FMT_I8>(h, cfg->kind, a, blocks, s); break;
-    case SCONE_FMT_I4: opt_launch_kind<SCONE_FMT_I4>(h, cfg->kind, a, blocks, s); break;
-    case SCONE_FMT_BF16: opt_launch_kind<SCONE_FMT_BF16>(h, cfg->kind, a, blocks, s); break;
-    case SCONE_FMT_MXFP4: opt_launch_kind<SCONE_FMT_MXFP4>(h, cfg->kind, a, blocks, s); break;
-    default: return scone_fail(h, SCONE_EINVAL, "scone_opt_step: bad format");
-  }
+  const unsigned blocks = opt_begin(h, n);
+  const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch_kind<decltype(F)::value>(h, cfg->kind, a, blocks, (hipStream_t)stream); });
+  if (bad) return scone_refuse(h, SCONE_EINVAL, who, "bad format");
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
 }

@@ -197,18 +197,6 @@ void lean_scalars(const scone_lean_cfg *cfg, scone_opt_scalars *out) {
   out->gscale = (float)cfg->grad_scale;
 }
 
-const char *fmt_name(int fmt) {
-  switch (fmt) {
-    case SCONE_FMT_F32: return "fp32";
-    case SCONE_FMT_F16: return "fp16";
-    case SCONE_FMT_I8: return "int8";
-    case SCONE_FMT_I4: return "int4";
-    case SCONE_FMT_BF16: return "bf16";
-    case SCONE_FMT_MXFP4: return "mxfp4";
-    default: return "unknown";
-  }
-}
-
 struct lean_args {
   const int64_t *ids;
   const float *grad;
@@ -247,32 +235,27 @@ extern "C" uint32_t scone_lean_rand16(uint64_t seed, int64_t step, uint64_t row_
 
 extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                                    uint64_t n, float *d_master, float *d_row_state, scone_stream_t stream) {
-  if (!h) return SCONE_EINVAL;
-  if (const char *bad = lean_check(cfg)) return scone_fail(h, SCONE_EINVAL, (std::string("scone_opt_step_lean: ") + bad).c_str());
-  if (h->cfg.dim == 0) return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: handle has no table (dim == 0)");
-  if (!h->rows) return scone_fail(h, SCONE_ESTATE, "scone_opt_step_lean: handle has no table");
+  const char *who = "scone_opt_step_lean";
+  SCONE_TRY(opt_need_table(h, who, lean_check(cfg)));
   const int fmt = h->cfg.table_fmt;
   const bool inplace = d_master == nullptr, stoch = cfg->rounding == SCONE_ROUND_STOCHASTIC;
   if (inplace && fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
-    return scone_fail(h, SCONE_EINVAL,
-                      (std::string("scone_opt_step_lean: in place (d_master == NULL) needs an fp32 or bf16 table, this one is ") +
-                       fmt_name(fmt)).c_str());
+    return scone_refuse(h, SCONE_EINVAL, who,
+                        (std::string("in place (d_master == NULL) needs an fp32 or bf16 table, this one is ") + scone_fmt_name(fmt)).c_str());
   if (stoch && !inplace)
-    return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: stochastic rounding with a master: there is nothing to round");
+    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding with a master: there is nothing to round");
   if (stoch && fmt != SCONE_FMT_BF16)
-    return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: stochastic rounding on an fp32 table: there is nothing to round");
+    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding on an fp32 table: there is nothing to round");
   if (n == 0) return SCONE_OK;
-  if (!d_row_ids || !d_grad_rows) return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: null pointer");
+  if (!d_row_ids || !d_grad_rows) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
   if (cfg->kind == SCONE_LEAN_ROWWISE_ADAGRAD && !d_row_state)
-    return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: row-wise Adagrad needs d_row_state (one fp32 per owned row)");
+    return scone_refuse(h, SCONE_EINVAL, who, "row-wise Adagrad needs d_row_state (one fp32 per owned row)");
   SCONE_ON_DEVICE(h);
-  if (h->stage) scone_stage_destroy(h);  // the table changes: as scone_opt_step (the staged cache of cold rows is dropped)
   lean_args a;
   a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state;
   a.rnd.seed = cfg->seed, a.rnd.step = cfg->step;
   lean_scalars(cfg, &a.sc);
-  unsigned blocks = scone_capped_blocks((n + 3) / 4);
-  if (h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks) blocks = (unsigned)h->opt_max_blocks;
+  const unsigned blocks = opt_begin(h, n);
   hipStream_t s = (hipStream_t)stream;
   if (inplace) {
     if (fmt == SCONE_FMT_F32)
@@ -281,16 +264,8 @@ extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, c
       lean_launch_kind<SCONE_FMT_BF16, true, true>(h, cfg->kind, a, blocks, s);
     else
       lean_launch_kind<SCONE_FMT_BF16, true, false>(h, cfg->kind, a, blocks, s);
-  } else {
-    switch (fmt) {
-      case SCONE_FMT_F32: lean_launch_kind<SCONE_FMT_F32, false, false>(h, cfg->kind, a, blocks, s); break;
-      case SCONE_FMT_F16: lean_launch_kind<SCONE_FMT_F16, false, false>(h, cfg->kind, a, blocks, s); break;
-      case SCONE_FMT_I8: lean_launch_kind<SCONE_FMT_I8, false, false>(h, cfg->kind, a, blocks, s); break;
-      case SCONE_FMT_I4: lean_launch_kind<SCONE_FMT_I4, false, false>(h, cfg->kind, a, blocks, s); break;
-      case SCONE_FMT_BF16: lean_launch_kind<SCONE_FMT_BF16, false, false>(h, cfg->kind, a, blocks, s); break;
-      case SCONE_FMT_MXFP4: lean_launch_kind<SCONE_FMT_MXFP4, false, false>(h, cfg->kind, a, blocks, s); break;
-      default: return scone_fail(h, SCONE_EINVAL, "scone_opt_step_lean: bad format");
-    }
+  } else if (scone_dispatch_fmt(fmt, [&](auto F) { lean_launch_kind<decltype(F)::value, false, false>(h, cfg->kind, a, blocks, s); })) {
+    return scone_refuse(h, SCONE_EINVAL, who, "bad format");
   }
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;

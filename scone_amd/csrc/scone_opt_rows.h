@@ -14,9 +14,21 @@
 
 constexpr int OPT_NT = 4;  // pieces per lane and block: 4 x 64 x 4 = 1024 elements
 
-__device__ __forceinline__ float opt_wave_max(float v) {
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
+// ---- the host side both entry points open with
+// the handle, then the cfg (bad_cfg: what the entry point's cfg check found, or null), then the table
+static inline int opt_need_table(scone_handle *h, const char *who, const char *bad_cfg) {
+  if (!h) return SCONE_EINVAL;
+  if (bad_cfg) return scone_refuse(h, SCONE_EINVAL, who, bad_cfg);
+  if (h->cfg.dim == 0) return scone_refuse(h, SCONE_EINVAL, who, "handle has no table (dim == 0)");
+  if (!h->rows) return scone_refuse(h, SCONE_ESTATE, who, "handle has no table");
+  return SCONE_OK;
+}
+// the table is about to change: as scone_table_store_f32_ids, the staged cache of cold rows is dropped.  Returns the grid for n
+// listed rows, a wave each (SCONE_OPT_MAX_BLOCKS caps it)
+static inline unsigned opt_begin(scone_handle *h, unsigned long long n) {
+  if (h->stage) scone_stage_destroy(h);
+  const unsigned blocks = scone_capped_blocks((n + 3) / 4);
+  return h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks ? (unsigned)h->opt_max_blocks : blocks;
 }
 
 __device__ __forceinline__ uint32_t opt_i8_word(const float4 &x, float sf) {
@@ -78,7 +90,7 @@ __device__ __forceinline__ float opt_i8_amax(float rowmax, const float4 &w) {
 // INT8, the whole row is the block in registers (pieces <= OPT_NT * 64): scale and payload.  Every lane calls this.
 __device__ __forceinline__ void opt_i8_store_block(const scone_row_store &st, __half *__restrict__ scales, unsigned long long lr, int p0,
                                                    int lane, const bool (&on)[OPT_NT], const float4 (&w)[OPT_NT], float rowmax) {
-  const __half sh = scone_q_scale(opt_wave_max(rowmax), 127.0f);
+  const __half sh = scone_q_scale(scone_wave_max(rowmax), 127.0f);
   const float sf = __half2float(sh);
   uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
 #pragma unroll
@@ -90,7 +102,7 @@ __device__ __forceinline__ void opt_i8_store_block(const scone_row_store &st, __
 // INT8, a wide row: read back from the master row W what THIS lane stored there.  Every lane calls this.
 __device__ __forceinline__ void opt_i8_store_wide(const scone_row_store &st, __half *__restrict__ scales, unsigned long long lr,
                                                   const float4 *W, int pieces, int lane, float rowmax) {
-  const __half sh = scone_q_scale(opt_wave_max(rowmax), 127.0f);
+  const __half sh = scone_q_scale(scone_wave_max(rowmax), 127.0f);
   const float sf = __half2float(sh);
   uint32_t *o = reinterpret_cast<uint32_t *>(st.row(lr));
   for (int p0 = 0; p0 < pieces; p0 += OPT_NT * 64) {

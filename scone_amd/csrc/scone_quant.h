@@ -17,6 +17,12 @@ __device__ __forceinline__ unsigned short scone_f32_to_bf16_bits(float x) {
   return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
+// the maximum over the wave's 64 lanes, in every lane (exact: no rounding, so the lane mapping cannot show)
+__device__ __forceinline__ float scone_wave_max(float v) {
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+  return v;
+}
+
 // INT8 (qmax = 127, amax over the row) and INT4 (qmax = 7, amax over a group of 128): the fp16 scale, and the integer of one
 // element as a float in [-qmax, qmax] (0 where the scale is 0 -- or NaN: the comparison is false)
 __device__ __forceinline__ __half scone_q_scale(float amax, float qmax) { return __float2half_rn(amax / qmax); }

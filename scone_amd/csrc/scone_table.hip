@@ -12,14 +12,7 @@
 #include "scone_common.h"
 #include "scone_quant.h"
 
-#include <type_traits>
-
 namespace {
-
-__device__ __forceinline__ float wave_max(float v) {
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
 
 // One wave per row.  src row index = blockIdx-derived r; destination local row =
 // (ids ? ids[r] : row0 + r) - row_begin.
@@ -51,7 +44,7 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
   } else if (FMT == SCONE_FMT_I8) {
     float m = 0.f;
     for (int e = lane; e < d; e += 64) m = fmaxf(m, fabsf(x[e]));
-    m = wave_max(m);
+    m = scone_wave_max(m);
     const __half sh = scone_q_scale(m, 127.0f);
     const float sf = __half2float(sh);
     int8_t *o = reinterpret_cast<int8_t *>(st.row(lr));
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(256) void k_store_f32(const float *__restrict__ src
     for (int grp = 0; grp < ng; ++grp) {
       const float a = x[grp * SCONE_I4_GROUP + 2 * lane];
       const float b = x[grp * SCONE_I4_GROUP + 2 * lane + 1];
-      const float m = wave_max(fmaxf(fabsf(a), fabsf(b)));
+      const float m = scone_wave_max(fmaxf(fabsf(a), fabsf(b)));
       const __half sh = scone_q_scale(m, 7.0f);
       const float sf = __half2float(sh);
       const int qa = (int)scone_q_elem(a, sf, 7.f), qb = (int)scone_q_elem(b, sf, 7.f);
@@ -212,25 +205,6 @@ __global__ __launch_bounds__(256) void k_gather_rows(scone_row_store st, const _
   }  // grid-stride loop over ids
 }
 
-template <typename F>
-int dispatch_fmt(int fmt, F &&f) {
-  switch (fmt) {
-    case SCONE_FMT_F32: f(std::integral_constant<int, SCONE_FMT_F32>()); return 0;
-    case SCONE_FMT_F16: f(std::integral_constant<int, SCONE_FMT_F16>()); return 0;
-    case SCONE_FMT_I8: f(std::integral_constant<int, SCONE_FMT_I8>()); return 0;
-    case SCONE_FMT_I4: f(std::integral_constant<int, SCONE_FMT_I4>()); return 0;
-    case SCONE_FMT_BF16: f(std::integral_constant<int, SCONE_FMT_BF16>()); return 0;
-    case SCONE_FMT_MXFP4: f(std::integral_constant<int, SCONE_FMT_MXFP4>()); return 0;
-    default: return -1;
-  }
-}
-
-int check_table(scone_handle *h, const char *who) {
-  if (!h) return SCONE_EINVAL;
-  if (h->cfg.dim <= 0 || !h->rows) return scone_fail(h, SCONE_ESTATE, who);
-  return SCONE_OK;
-}
-
 // the staged-prefetch state caches the scales of the HBM-resident head: drop it when the table changes
 void table_modified(scone_handle *h) {
   if (h->stage) scone_stage_destroy(h);
@@ -294,8 +268,7 @@ void scales_reorder_host(const scone_handle *h, void *s, uint64_t n_rows, bool t
 
 extern "C" int scone_table_upload(scone_handle *h, const void *rows, const void *scales, uint64_t row0, uint64_t nrows,
                                   int src_is_device, scone_stream_t stream) {
-  int rc = check_table(h, "scone_table_upload: handle has no table (dim == 0)");
-  if (rc) return rc;
+  SCONE_TRY(scone_need_table(h, "scone_table_upload"));
   if (nrows == 0) return SCONE_OK;
   if (!rows) return scone_fail(h, SCONE_EINVAL, "scone_table_upload: null rows");
   if (h->scale_bytes_per_row && !scales) return scone_fail(h, SCONE_EINVAL, "scone_table_upload: format needs scales");
@@ -329,8 +302,7 @@ extern "C" int scone_table_upload(scone_handle *h, const void *rows, const void 
 
 extern "C" int scone_table_download(scone_handle *h, void *rows, void *scales, uint64_t row0, uint64_t nrows,
                                     int dst_is_device, scone_stream_t stream) {
-  int rc = check_table(h, "scone_table_download: handle has no table (dim == 0)");
-  if (rc) return rc;
+  SCONE_TRY(scone_need_table(h, "scone_table_download"));
   if (nrows == 0) return SCONE_OK;
   if (!rows) return scone_fail(h, SCONE_EINVAL, "scone_table_download: null rows");
   if (h->scale_bytes_per_row && !scales) return scone_fail(h, SCONE_EINVAL, "scone_table_download: format has scales");
@@ -367,7 +339,7 @@ extern "C" int scone_table_download(scone_handle *h, void *rows, void *scales, u
 int scone_store_f32_into(scone_handle *h, const scone_row_store &st, void *scales, uint64_t row_begin, uint64_t row_end,
                          const float *d_src, const int64_t *d_ids, uint64_t row0, uint64_t nrows, hipStream_t s) {
   const unsigned blocks = scone_capped_blocks((nrows + 3) / 4);
-  int bad = dispatch_fmt(h->cfg.table_fmt, [&](auto F) {
+  int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) {
     hipLaunchKernelGGL((k_store_f32<decltype(F)::value>), dim3(blocks), dim3(256), 0, s, d_src, d_ids,
                        (unsigned long long)row0, (unsigned long long)nrows, (unsigned long long)row_begin,
                        (unsigned long long)row_end, h->cfg.dim, st, (__half *)scales, h->d_status);
@@ -381,7 +353,7 @@ int scone_fill_synth_into(scone_handle *h, const scone_row_store &st, void *scal
                           uint32_t seed, float base_scale, hipStream_t s) {
   if (nrows == 0) return SCONE_OK;
   const unsigned blocks = scone_capped_blocks((nrows + 3) / 4);
-  int bad = dispatch_fmt(h->cfg.table_fmt, [&](auto F) {
+  int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) {
     hipLaunchKernelGGL((k_fill_synth<decltype(F)::value>), dim3(blocks), dim3(256), 0, s, (unsigned long long)row_begin,
                        (unsigned long long)nrows, h->cfg.dim, seed, base_scale, st, (__half *)scales);
   });
@@ -401,8 +373,7 @@ static int store_f32_common(scone_handle *h, const float *d_src, const int64_t *
 
 extern "C" int scone_table_store_f32(scone_handle *h, const float *d_rows_f32, uint64_t row0, uint64_t nrows,
                                      scone_stream_t stream) {
-  int rc = check_table(h, "scone_table_store_f32: handle has no table (dim == 0)");
-  if (rc) return rc;
+  SCONE_TRY(scone_need_table(h, "scone_table_store_f32"));
   if (row0 < h->cfg.row_begin || row0 + nrows > h->cfg.row_end)
     return scone_fail(h, SCONE_ERANGE, "scone_table_store_f32: rows outside [row_begin,row_end)");
   return store_f32_common(h, d_rows_f32, nullptr, row0, nrows, (hipStream_t)stream);
@@ -410,32 +381,27 @@ extern "C" int scone_table_store_f32(scone_handle *h, const float *d_rows_f32, u
 
 extern "C" int scone_table_store_f32_ids(scone_handle *h, const float *d_rows_f32, const int64_t *d_ids,
                                          uint64_t nrows, scone_stream_t stream) {
-  int rc = check_table(h, "scone_table_store_f32_ids: handle has no table (dim == 0)");
-  if (rc) return rc;
+  SCONE_TRY(scone_need_table(h, "scone_table_store_f32_ids"));
   if (nrows && !d_ids) return scone_fail(h, SCONE_EINVAL, "scone_table_store_f32_ids: null ids");
   return store_f32_common(h, d_rows_f32, d_ids, 0, nrows, (hipStream_t)stream);
 }
 
 extern "C" int scone_table_fill_synthetic(scone_handle *h, uint32_t seed, float base_scale, scone_stream_t stream) {
-  int rc = check_table(h, "scone_table_fill_synthetic: handle has no table (dim == 0)");
-  if (rc) return rc;
+  SCONE_TRY(scone_need_table(h, "scone_table_fill_synthetic"));
   SCONE_ON_DEVICE(h);
   table_modified(h);
-  rc = scone_fill_synth_into(h, scone_store_of(h), h->scales, h->cfg.row_begin, h->local_rows, seed, base_scale,
-                             (hipStream_t)stream);
-  if (rc) return rc;
+  SCONE_TRY(scone_fill_synth_into(h, scone_store_of(h), h->scales, h->cfg.row_begin, h->local_rows, seed, base_scale, (hipStream_t)stream));
   return scone_shard_fill_head_synth(h, seed, base_scale, (hipStream_t)stream);  // the replicated head of a shard, if any
 }
 
 extern "C" int scone_table_gather_rows(scone_handle *h, const int64_t *d_ids, uint64_t n, float *d_out,
                                        scone_stream_t stream) {
-  int rc = check_table(h, "scone_table_gather_rows: handle has no table (dim == 0)");
-  if (rc) return rc;
+  SCONE_TRY(scone_need_table(h, "scone_table_gather_rows"));
   if (n == 0) return SCONE_OK;
   if (!d_ids || !d_out) return scone_fail(h, SCONE_EINVAL, "scone_table_gather_rows: null pointer");
   SCONE_ON_DEVICE(h);
   const unsigned blocks = scone_capped_blocks((n + 3) / 4);
-  int bad = dispatch_fmt(h->cfg.table_fmt, [&](auto F) {
+  int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) {
     hipLaunchKernelGGL((k_gather_rows<decltype(F)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        scone_store_of(h), (const __half *)h->scales, d_ids, (unsigned long long)n,
                        (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, d_out,
