@@ -830,6 +830,33 @@ int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_
                         uint64_t n, float *d_master /* NULL: in place */, float *d_row_state /* fp32 [row_end - row_begin] */,
                         scone_stream_t stream);
 
+/* ---- backward applied in place: scone_backward_rows and the in-place scone_opt_step_lean in ONE pass (new here; FBGEMM /
+ * TorchRec fuse an embedding table's backward with its optimizer the same way).  Appended: SCONE_ABI_VERSION is unchanged, and
+ * every entry point above is as it was.  The table gradient -- fp32 [U, d], the one table-sized-per-batch array of in-place
+ * training -- is never stored: there is no grad_rows and no row_ids output, and no device buffer is sized by U * d.
+ * Contract.  After the call the table rows and d_row_state hold exactly the bits that
+ *   scone_backward_rows(h, plan, d_grad_out, grad_dtype, reduce, ids, rows, U), then
+ *   scone_opt_step_lean(h, cfg, ids, rows, U, NULL, d_row_state)
+ * leave with the same arguments; a row the plan does not list keeps every bit.  So the gradient's order (reference order,
+ * chunks of scone_backward_chunk(), partials in chunk order), the update's per-element arithmetic, the order of the row-wise
+ * sum (lane (j / 4) % 64, ascending j, the butterfly) and the stochastic bits (keyed by the GLOBAL row id and the column) are
+ * the ones stated under "backward" and "lean optimizer step".
+ * In-place mode only: SCONE_FMT_F32 and SCONE_FMT_BF16 tables; master mode stays with the two calls.  HBM, a pinned-host table
+ * with a hot head and a row-sharded handle all work (the rows go through the handle's own row store); the plan may come from
+ * any of the three plan calls, in both lookup modes.  Every d % 8 == 0 up to 4096 is fused: a wave keeps the finished gradient
+ * row in its share of LDS.  d > 4096 returns SCONE_EINVAL naming the two calls above, which have no such limit.
+ * The call is stream-ordered: it does not synchronise and allocates nothing.  A staged-prefetch cache is dropped first, as
+ * scone_opt_step_lean does.  An empty plan (U == 0) is a no-op.  At most two kernel launches: the first, only when the plan
+ * has rows with several chunks, fills the plan's partials of those rows, a wavefront per chunk; the second is the fused
+ * kernel, a wavefront per touched row, its grid capped as scone_opt_step's (SCONE_OPT_MAX_BLOCKS applies).  Plain vector
+ * stores only and no atomics: plan rows are owned, distinct and ascending, so no id is checked and no status bit can rise.
+ * The plan's partials are scratch of the call: as with scone_backward_rows, one plan is used by one host thread at a time.
+ * SCONE_EINVAL (scone_last_error names the reason, prefixed "scone_backward_apply_lean: "): what scone_opt_step_lean says of
+ * a cfg, a handle with dim == 0, a null plan / d_grad_out, a plan of another handle, a bad grad_dtype / reduce, a table that is
+ * not fp32 / bf16 (the format is named), stochastic rounding on an fp32 table, row-wise Adagrad without d_row_state, d > 4096. */
+int scone_backward_apply_lean(scone_handle *h, scone_bwd_plan *plan, const void *d_grad_out, int32_t grad_dtype, int32_t reduce,
+                              const scone_lean_cfg *cfg, float *d_row_state, scone_stream_t stream);
+
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
  * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.

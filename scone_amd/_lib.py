@@ -193,6 +193,7 @@ SIGNATURES = {
     "scone_lean_scalars_of": (C.c_int, [C.POINTER(LeanCfg), C.POINTER(OptScalars)]),
     "scone_lean_rand16": (_U32, [_U64, _I64, _U64, _U32]),
     "scone_opt_step_lean": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _U64, _P, _P, _P]),
+    "scone_backward_apply_lean": (C.c_int, [_P, _P, _P, _I32, _I32, C.POINTER(LeanCfg), _P, _P]),
 }
 
 _lock = threading.Lock()

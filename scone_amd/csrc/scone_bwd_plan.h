@@ -1,0 +1,126 @@
+// What the backward's kernels share -- k_bwd_chunks / k_bwd_combine (scone_backward.hip) and the fused backward + lean step
+// (scone_backward_apply.hip): the plan a batch is cut into, and how one wave walks the references of a chunk.
+//
+// A plan is the sorted reference stream of a batch: the references of a row are consecutive, in (p, k) order, cut into chunks of
+// SCONE_BWD_CHUNK; a row with several chunks has a partial slot per chunk and one bwd_multi entry.  The order in which a chunk's
+// references are added (bwd_walk) and the order in which a row's partials are added (chunk order) are the gradient's contract.
+#pragma once
+
+#include "scone_common.h"
+
+#ifndef SCONE_BWD_CHUNK
+#define SCONE_BWD_CHUNK 128  // part of the contract (scone_backward_chunk); chosen by measurement, DESIGN.md 4.4b
+#endif
+static_assert(SCONE_BWD_CHUNK >= 64 && SCONE_BWD_CHUNK <= 512 && (SCONE_BWD_CHUNK & (SCONE_BWD_CHUNK - 1)) == 0,
+              "SCONE_BWD_CHUNK: a power of two in [64, 512]");
+
+// device-side totals of a plan, copied to the host by the plan's one synchronisation
+struct bwd_meta {
+  uint32_t n_refs;    // references (owned rows only)
+  uint32_t n_segs;    // U: distinct rows with a reference
+  uint32_t n_chunks;  // work items of the chunk pass
+  uint32_t n_multi;   // rows with more than one chunk
+  uint32_t n_slots;   // partial slots = chunks of those rows
+  uint32_t pad[3];
+};
+
+// one work item of the chunk pass: references [begin, begin + count) of the sorted stream go to row `dest` of grad_rows
+// (partial == 0) or to partial slot `dest` (partial == 1)
+struct __attribute__((aligned(16))) bwd_chunk {
+  uint32_t begin, count, dest, partial;
+};
+// one row with several chunks: grad_rows[seg] = partial[slot0] + ... + partial[slot0 + n - 1], in that order
+struct __attribute__((aligned(16))) bwd_multi {
+  uint32_t seg, slot0, n, pad;
+};
+
+struct scone_bwd_plan {
+  scone_handle *h = nullptr;
+  int device = 0;
+  int dim = 0;
+  long long ntok = 0;
+  bwd_meta m = {};
+  // kept for the life of the plan
+  int32_t *d_kfull = nullptr;     // [ntok] K_p, the full hit count
+  float *d_w = nullptr;           // [ntok] 1.0f / (float)K_p (1.0f where K_p == 0: never read)
+  uint32_t *d_ref_p = nullptr;    // [max_refs] position of every reference, sorted stably by row
+  uint32_t *d_row_id = nullptr;   // [seg_cap + 1] row of segment u
+  bwd_chunk *d_chunks = nullptr;  // [chunk_cap]
+  bwd_multi *d_multi = nullptr;   // [multi_cap]
+  float *d_partial = nullptr;     // [n_slots, dim]
+  bwd_meta *d_meta = nullptr;
+};
+
+// 16 bytes of grad_out as fp32: 4 elements (fp32) or 8 (fp16 / bf16); every conversion is exact
+template <int DT>
+struct bwd_piece {
+  static constexpr int E = DT == SCONE_DT_F32 ? 4 : 8;
+  static __device__ __forceinline__ void to_f32(const uint4 &r, float *f) {
+    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+    if constexpr (DT == SCONE_DT_F32) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) f[i] = __uint_as_float(w[i]);
+    } else if constexpr (DT == SCONE_DT_F16) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        f[2 * i] = __half2float(__ushort_as_half((unsigned short)(w[i] & 0xFFFFu)));
+        f[2 * i + 1] = __half2float(__ushort_as_half((unsigned short)(w[i] >> 16)));
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        f[2 * i] = __uint_as_float(w[i] << 16);
+        f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+      }
+    }
+  }
+};
+
+// RR references of a chunk: their positions and weights are wave-uniform scalars, their RR * NT loads are independent, and only
+// the adds form a chain -- in reference order, which is the contract.
+template <int DT, int NT, bool MEAN, int RR>
+__device__ __forceinline__ void bwd_walk(const uint32_t *__restrict__ ref_p, const float *__restrict__ w, const uint8_t *gl,
+                                         size_t row_bytes, const bool (&on)[NT], float (&acc)[NT][bwd_piece<DT>::E]) {
+  constexpr int E = bwd_piece<DT>::E;
+  uint4 raw[RR][NT];
+  float wr[RR];
+#pragma unroll
+  for (int r = 0; r < RR; ++r) {
+    const uint32_t p = ref_p[r];
+    wr[r] = MEAN ? w[p] : 1.0f;
+    const uint8_t *row = gl + (size_t)p * row_bytes;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (on[t]) raw[r][t] = *reinterpret_cast<const uint4 *>(row + (size_t)t * 1024);
+  }
+#pragma unroll
+  for (int r = 0; r < RR; ++r) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (on[t]) {
+        float f[E];
+        bwd_piece<DT>::to_f32(raw[r][t], f);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const float cc = MEAN ? f[e] * wr[r] : f[e];
+          acc[t][e] = acc[t][e] + cc;
+        }
+      }
+    }
+  }
+}
+
+// All the references of one chunk for one column tile of NT * 64 pieces: 16 / NT at a time (16 independent 16-byte loads per lane
+// in flight whatever the tile width: a chunk of a hot row is one dependent chain of memory latencies otherwise), what is left
+// four at a time, then one by one.  `acc` starts at +0.0f.
+template <int DT, int NT, bool MEAN>
+__device__ __forceinline__ void bwd_walk_chunk(const uint32_t *__restrict__ rp, uint32_t count, const float *__restrict__ w,
+                                               const uint8_t *gl, size_t row_bytes, const bool (&on)[NT],
+                                               float (&acc)[NT][bwd_piece<DT>::E]) {
+  constexpr int R = 16 / NT;
+  uint32_t i = 0;
+  if constexpr (R > 4)
+    for (; i + R <= count; i += R) bwd_walk<DT, NT, MEAN, R>(rp + i, w, gl, row_bytes, on, acc);
+  for (; i + 4 <= count; i += 4) bwd_walk<DT, NT, MEAN, 4>(rp + i, w, gl, row_bytes, on, acc);
+  for (; i < count; ++i) bwd_walk<DT, NT, MEAN, 1>(rp + i, w, gl, row_bytes, on, acc);
+}

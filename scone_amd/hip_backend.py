@@ -349,6 +349,7 @@ def opt_scalars(kind, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_s
 
 _LEAN = {"sgd": L.LEAN_SGD, "rowwise_adagrad": L.LEAN_ROWWISE_ADAGRAD}
 _ROUND = {"nearest": L.ROUND_NEAREST, "stochastic": L.ROUND_STOCHASTIC}
+APPLY_LEAN_MAX_DIM = 4096     # the widest row scone_backward_apply_lean fuses (a wave's gradient row lives in its share of LDS)
 
 
 def _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step) -> "L.LeanCfg":
@@ -446,6 +447,49 @@ class BackwardPlan:
         if self.n_rows:
             grad_out.record_stream(torch.cuda.current_stream(t.device))    # it may be a temporary of the caller
         return ids[:self.n_rows], rows[:self.n_rows]
+
+    def apply_lean(self, grad_out: torch.Tensor, reduce: str = "mean", *, kind, lr: float,
+                   row_state: Optional[torch.Tensor] = None, eps: float = 1e-10, weight_decay: float = 0.0,
+                   grad_scale: float = 1.0, rounding="nearest", seed: int = 0, step: int = 1) -> int:
+        """``scone_backward_apply_lean``: the backward applied IN PLACE (include/scone_hip.h, "backward applied in place").  The
+        served fp32 / bf16 rows and ``row_state`` end with exactly the bits that :meth:`rows` followed by
+        :meth:`SconeTable.opt_step_lean` (``master=None``) leaves, but the fp32 ``[U, d]`` gradient is never stored.  The
+        arguments are those two calls'.  Stream-ordered, at most two kernel launches, no allocation.  A table wider than
+        ``APPLY_LEAN_MAX_DIM`` takes the two calls (the library does not fuse it).  Returns ``n_rows``."""
+        plan, t = self._plan(), self._table
+        cfg = _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step)
+        if t.fmt not in (L.FMT_F32, L.FMT_BF16):
+            raise ValueError(f"apply_lean: in place needs an fp32 or bf16 table, this one has format code {t.fmt}")
+        if cfg.rounding == L.ROUND_STOCHASTIC and t.fmt != L.FMT_BF16:
+            raise ValueError("apply_lean: stochastic rounding is for bf16 rows (on an fp32 table there is nothing to round)")
+        owned = t.row_end - t.row_begin
+        if row_state is None:
+            if cfg.kind == L.LEAN_ROWWISE_ADAGRAD:
+                raise ValueError("apply_lean: this kind needs row_state")
+        elif not (isinstance(row_state, torch.Tensor) and row_state.dtype == torch.float32 and tuple(row_state.shape) == (owned,)
+                  and row_state.device == t.device and row_state.is_contiguous()):
+            raise ValueError(f"apply_lean: row_state must be a contiguous fp32 [{owned}] tensor on {t.device} (it is updated in place)")
+        if grad_out.dtype not in _DT:
+            raise ValueError(f"grad_out must be fp32, fp16 or bf16, not {grad_out.dtype}")
+        if grad_out.numel() != self.ntok * t.dim or (grad_out.dim() and grad_out.shape[-1] != t.dim and grad_out.numel()):
+            raise ValueError(f"grad_out must hold [{self.ntok}, {t.dim}] elements, got {tuple(grad_out.shape)}")
+        if reduce not in _REDUCE:
+            raise ValueError(f"unknown reduce {reduce!r}")
+        if t.dim > APPLY_LEAN_MAX_DIM:                           # the two-call road, the same bits
+            ids, rows = self.rows(grad_out, reduce)
+            t.opt_step_lean(ids, rows, kind=kind, lr=lr, row_state=row_state, eps=eps, weight_decay=weight_decay,
+                            grad_scale=grad_scale, rounding=rounding, seed=seed, step=step)
+            return self.n_rows
+        if not (grad_out.is_cuda and grad_out.device == t.device and grad_out.is_contiguous()):
+            grad_out = grad_out.to(device=t.device).contiguous()
+        with torch.cuda.device(t.device):
+            stream = torch.cuda.current_stream(t.device)
+            rc = L.lib().scone_backward_apply_lean(t._h, plan, grad_out.data_ptr(), _DT[grad_out.dtype], _REDUCE[reduce],
+                                                   C.byref(cfg), _ptr(row_state), stream.cuda_stream)
+        t._check(rc, "scone_backward_apply_lean")
+        if self.n_rows:
+            grad_out.record_stream(stream)                       # it may be a temporary of the caller
+        return self.n_rows
 
     def counts(self) -> torch.Tensor:
         """``scone_backward_counts``: ``K_p``, the full hit count of every position, int32 ``[ntok]``."""

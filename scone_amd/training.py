@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from scone_amd import _lib
+from scone_amd.hip_backend import APPLY_LEAN_MAX_DIM
 from scone_amd.inference.embedding_cache import EmbeddingCache
 
 
@@ -68,8 +69,11 @@ class _Lookup(torch.autograd.Function):
         table = module.cache.to_device()
         grad_weight = grad_base = None
         grad_out = grad_out.contiguous()
+        fused = getattr(module, "_fused_opt", None)           # an FGramOptimizer(fused_backward=True): the update happens here
         with table.backward_plan(ctx.tok, ctx.cu) as plan:
-            if ctx.needs_input_grad[0]:
+            if ctx.needs_input_grad[0] and fused is not None:
+                fused._apply_backward(plan, grad_out, ctx.reduce)
+            elif ctx.needs_input_grad[0]:
                 row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
                 # set on the module, not returned: autograd's accumulation re-creates a sparse gradient without its coalesced flag
                 module._accumulate(row_ids, grad_rows)
@@ -150,6 +154,7 @@ class InPlaceFGramTable(nn.Module):
         self.shape = (table.n_rows, table.dim)
         self.anchor = nn.Parameter(torch.zeros(0, dtype=torch.float32, device=table.device))
         self.grad = None
+        self._fused_opt = None          # set by FGramOptimizer(fused_backward=True)
 
     def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
                 out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -178,10 +183,18 @@ class FGramOptimizer:
     ``state2`` is fp32 ``[N]``.  On a :class:`TrainableFGramTable` it updates the fp32 master and re-stores the served rows, as
     the other kinds do.  On an :class:`InPlaceFGramTable` (``"sgd"`` or ``"rowwise_adagrad"`` only, an fp32 or bf16 cache only)
     the served rows themselves are updated; ``rounding="stochastic"`` (bf16 rows) draws its bits from ``seed``, the step count
-    ``t``, the row id and the column, so a run is reproducible and a resumed one (``state_dict``) continues it."""
+    ``t``, the row id and the column, so a run is reproducible and a resumed one (``state_dict``) continues it.
+
+    ``fused_backward=True`` (an :class:`InPlaceFGramTable` of ``d <= 4096`` only; include/scone_hip.h, "backward applied in
+    place").  The lookup's backward itself updates the served rows, so the fp32 ``[U, d]`` gradient is never stored:
+    ``module.grad`` stays ``None``, ``t`` advances once per backward, and the update reads ``lr``, ``eps``, ``weight_decay`` and
+    the attribute ``grad_scale`` at backward time.  TWO BACKWARDS ARE TWO UPDATES -- nothing is left to accumulate into -- so
+    gradient accumulation over micro-batches needs the default road.  ``step()`` only returns the number of rows updated since
+    the last ``step()`` (its ``grad_scale`` argument is not used) and ``zero_grad()`` has nothing to do.  One backward of this
+    road leaves the bits one backward + ``step(grad_scale)`` of the default road leaves."""
 
     def __init__(self, module, kind: str = "adam", lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, rounding: str = "nearest", seed: int = 0) -> None:
+                 weight_decay: float = 0.0, rounding: str = "nearest", seed: int = 0, fused_backward: bool = False) -> None:
         self.in_place = isinstance(module, InPlaceFGramTable)
         kinds = ("sgd", "rowwise_adagrad") if self.in_place else ("sgd", "adagrad", "adam", "rowwise_adagrad")
         if kind not in kinds:
@@ -201,8 +214,39 @@ class FGramOptimizer:
         self.rounding, self.seed = rounding, int(seed)
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.t = 0
+        self.grad_scale = 1.0                          # fused_backward: read at backward time
+        self.fused_backward = False
+        self._fused_rows = 0                           # rows updated by fused backwards since the last step()
+        self._set_fused(fused_backward)
         self.state1: Optional[torch.Tensor] = None     # Adam's m
         self.state2: Optional[torch.Tensor] = None     # Adam's v / Adagrad's sum of squares
+
+    def _set_fused(self, on: bool) -> None:
+        on = bool(on)
+        if on:
+            if not self.in_place:
+                raise ValueError("fused_backward is for an InPlaceFGramTable: a TrainableFGramTable's master rows are updated by "
+                                 "step()")
+            dim = self.module.cache.to_device().dim
+            if dim > APPLY_LEAN_MAX_DIM:
+                raise ValueError(f"fused_backward needs d <= {APPLY_LEAN_MAX_DIM}, this table has d = {dim}")
+            other = self.module._fused_opt
+            if other is not None and other is not self and other.fused_backward:
+                other.fused_backward = False           # one optimizer updates a module
+        if self.in_place and (on or self.module._fused_opt is self):
+            self.module._fused_opt = self if on else None
+        self.fused_backward = on
+
+    @torch.no_grad()
+    def _apply_backward(self, plan, grad_out: torch.Tensor, reduce: str) -> None:
+        """One update, from inside the lookup's backward (``fused_backward=True``)."""
+        table = self.module.cache.to_device()
+        self.t += 1
+        self._ensure_state()
+        state = None if self.state2 is None else self.state2[table.row_begin:table.row_end]
+        self._fused_rows += plan.apply_lean(grad_out, reduce, kind=self.kind, lr=self.lr, row_state=state, eps=self.eps,
+                                            weight_decay=self.weight_decay, grad_scale=self.grad_scale, rounding=self.rounding,
+                                            seed=self.seed, step=self.t)
 
     def _ensure_state(self) -> None:
         if self.kind == "rowwise_adagrad":
@@ -255,6 +299,9 @@ class FGramOptimizer:
 
     def _step_in_place(self, grad_scale: float) -> int:
         module = self.module
+        if self.fused_backward:                          # the backwards have updated the rows already
+            n, self._fused_rows = self._fused_rows, 0
+            return n
         if module.grad is None:
             return 0
         row_ids, grad_rows = module.grad
@@ -289,6 +336,7 @@ class FGramOptimizer:
     def state_dict(self) -> dict:
         return {"kind": self.kind, "t": self.t, "lr": self.lr, "betas": self.betas, "eps": self.eps,
                 "weight_decay": self.weight_decay, "rounding": self.rounding, "seed": self.seed,
+                "fused_backward": self.fused_backward, "grad_scale": self.grad_scale,
                 "state1": None if self.state1 is None else self.state1.clone(),
                 "state2": None if self.state2 is None else self.state2.clone()}
 
@@ -301,6 +349,8 @@ class FGramOptimizer:
         if rounding == "stochastic" and not (self.in_place and self.module.cache.to_device().fmt == _lib.FMT_BF16):
             raise ValueError("a state with stochastic rounding is for an InPlaceFGramTable on a bf16 cache")
         self.rounding, self.seed = rounding, int(state.get("seed", 0))
+        self._set_fused(state.get("fused_backward", False))
+        self.grad_scale = float(state.get("grad_scale", 1.0))
         table = self.module.cache.to_device()
         shape = (table.n_rows,) if self.kind == "rowwise_adagrad" else (table.n_rows, table.dim)
         for name in ("state1", "state2"):
