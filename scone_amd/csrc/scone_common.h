@@ -121,7 +121,7 @@ __host__ __device__ inline int scone_i4_scale_slot(int g, int d) { return d == 1
 // Every other d: logical order.  Hidden from the C ABI exactly as the INT4 slots are.
 __host__ __device__ inline int scone_mx_scale_slot(int b, int d) { return d == 1024 ? (((b & 15) << 1) | (b >> 4)) : b; }
 #define SCONE_MX_BLOCK 32
-// The format's definition in plain arithmetic (the lookup kernels use the hardware convert, scone_gather_impl.h mx_accumulate,
+// The format's definition in plain arithmetic (the lookup kernels use the hardware convert, scone_row_codec.h mx_accumulate,
 // which the exhaustive GPU test holds to this): E2M1 nibble -> fp32, E8M0 byte -> fp32 factor, value = their IEEE product.
 __host__ __device__ inline float scone_mx_elem(uint32_t nib) {
   const uint32_t m = nib & 7u;  // 0, 0.5, then (1 + m0 / 2) 2^((m >> 1) - 1): bits (m << 22) + (126 << 23)

@@ -77,59 +77,6 @@ template <> struct pack_io<__hip_bfloat16> {
   }
 };
 
-// acc[e] = fma(sc, q_e, acc[e]) for the 8 offset-binary nibbles of w, in 2.5 instead of 4 VALU ops per element:
-// w ^ 0x88888888 turns every nibble into two's complement; with a nibble in the HIGH half of a byte the
-// sign-extending byte convert (v_cvt_f32_i32 sext(BYTE_k), one SDWA instruction) yields 16 q, and
-// fma(sc / 16, 16 q, acc) equals fma(sc, q, acc) bit for bit (sc / 16 and the product are exact).
-__device__ __forceinline__ void i4_accumulate(uint32_t w, float sc, float *acc) {
-  const uint32_t t = w ^ 0x88888888u;
-  const uint32_t ev = (t << 4) & 0xF0F0F0F0u;  // elements 0, 2, 4, 6 in bytes 0..3
-  const uint32_t od = t & 0xF0F0F0F0u;         // elements 1, 3, 5, 7
-  const float sc16 = sc * 0.0625f;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int qe = (int)(ev << (24 - 8 * b)) >> 24;
-    const int qo = (int)(od << (24 - 8 * b)) >> 24;
-    acc[2 * b] = fmaf(sc16, (float)qe, acc[2 * b]);
-    acc[2 * b + 1] = fmaf(sc16, (float)qo, acc[2 * b + 1]);
-  }
-}
-
-// bf16 rows (a bf16 is the upper half of its fp32: the value is bits << 16): acc[a], acc[a + 1] += the two elements of row
-// word w[k], k = 0 .. K - 1 in list order.  The shift and the mask have no operand but the loaded word, so left to itself the
-// scheduler unpacks every row as it arrives and the live registers of a token double (fp16 rows stay packed until their
-// convert + add: at d = 768, max_n = 3 that was 72 VGPRs with 44 B of scratch against the fp16 twin's 67 without).  The empty
-// asm statements emit nothing; they make the unpack of row k wait for the sum of rows 0 .. k - 1, and the first row of a
-// column for the column before it (`prev`), which is the order the compiler picks for fp16 by itself: one accumulator pair
-// in flight, the rows packed.  The arithmetic is the plain list-order sum.
-template <int K, int STRIDE>
-__device__ __forceinline__ void bf16_accumulate_column(const uint32_t *w, float &lo, float &hi, const float *prev) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    uint32_t ww = w[k * STRIDE];
-    if (k > 0)
-      asm("" : "+v"(ww) : "v"(lo), "v"(hi));
-    else if (prev)
-      asm("" : "+v"(ww) : "v"(prev[0]), "v"(prev[1]));
-    lo += __uint_as_float(ww << 16);
-    hi += __uint_as_float(ww & 0xFFFF0000u);
-  }
-}
-
-// sum / K of a lane's elements.  fp32 / fp16 / bf16 tables can hold anything (a sum may overflow, be subnormal, inf or NaN;
-// a bf16 row spans fp32's whole exponent range): the full IEEE quotient -- the `else` below is theirs, and a new format
-// belongs there unless its sums are provably in range (MXFP4 spans fp32's whole range too: the full quotient, in the form that
-// lets the zero sums of that format pass, scone_mean_div_of_sum).  A sum of INT8 / INT4 rows is +0 or a multiple of 2^-24 far below
-// overflow, where the short form IS the IEEE quotient (scone_mean_div.h).
-template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const int n, const int k) {
-  if constexpr (FMT == SCONE_FMT_I8 || FMT == SCONE_FMT_I4)
-    scone_mean_div_in_range(acc, n, k);
-  else if constexpr (FMT == SCONE_FMT_MXFP4)
-    scone_mean_div_of_sum(acc, n, k);  // the full quotient; acc is a sum started at +0, and zero sums are common in this format
-  else
-    scone_mean_div(acc, n, k);
-}
-
 // Lane <-> element map.  A row is cut into segments of 512 elements; inside a segment lane l owns
 // 8 consecutive elements (4 in a trailing 256-element segment).  With this map every wave
 // instruction -- INT8 row loads (8 or 4 B/lane), fp16 wte / wpe loads and output stores
@@ -139,8 +86,7 @@ template <int FMT> __device__ __forceinline__ void mean_div(float *acc, const in
 template <int FMT, int D> struct wave_geom {
   static constexpr int EPL = D / 64;  // elements per lane
   static constexpr int NSEG = (D + 511) / 512;
-  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_MXFP4, "unknown table format");
-  static constexpr int BPE4 = FMT == SCONE_FMT_F32 ? 16 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 8 : FMT == SCONE_FMT_I8 ? 4 : 2;  // bytes per 4 elements (last arm: INT4 and MXFP4)
+  static constexpr int BPE4 = row_codec<FMT>::BPE4;  // bytes per 4 elements
   static constexpr int ROW_BYTES = D / 4 * BPE4;
   static constexpr int NBR = ROW_BYTES / 64;  // row bytes per lane
   static constexpr int seg_elems(int s) { return ((D - 512 * s) >= 512 ? 512 : (D - 512 * s)) / 64; }  // per lane
@@ -149,7 +95,7 @@ template <int FMT, int D> struct wave_geom {
   static constexpr int seg_row_words(int s) { return seg_elems(s) * BPE4 / 16; }
   static constexpr int seg_row_word0(int s) { return 8 * s * BPE4 / 16; }
   static constexpr bool OK = (D % 256 == 0) && (D <= 1280) && (seg_elems(NSEG - 1) * BPE4 % 16 == 0) &&
-                             (FMT != SCONE_FMT_I4 || SCONE_I4_GROUP % 8 == 0) && (FMT != SCONE_FMT_MXFP4 || SCONE_MX_BLOCK % 8 == 0);
+                             row_codec<FMT>::SCALE_SPAN % 8 == 0;  // a lane's run of 8 (or 4) elements has one scale
 };
 
 // waves per SIMD to ask of the register allocator: rows in flight (NC x NBR/4) + wte/wpe/out words +
@@ -271,6 +217,7 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
                                             uint8_t *out_row, uint32_t lane,
                                             const uint32_t *__restrict__ wpe_lds = nullptr) {
   using G = wave_geom<FMT, D>;
+  using C = row_codec<FMT>;
   constexpr int EPL = G::EPL, NWR = G::NBR / 4, NSEG = G::NSEG;
   constexpr int NWO = EPL * (int)sizeof(OutT) / 4;
   constexpr int OPW = pack_io<OutT>::PER_WORD;
@@ -308,29 +255,12 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
 #pragma unroll
       for (int i = 0; i < G::seg_row_words(s); ++i)  // wave-uniform choice between a plain and a streaming load
         raw[k][G::seg_row_word0(s) + i] = lr >= SCONE_NT_FROM_ROW ? __builtin_nontemporal_load(p + i) : p[i];
-      if constexpr (FMT == SCONE_FMT_I8) {
-        scw[k][s] = s == 0 ? reinterpret_cast<const uint32_t *>(scales_v)[lr >> 1] : 0u;  // two half scales per word (scalar load)
-      } else if constexpr (FMT == SCONE_FMT_I4) {
-        if constexpr (D == 1024) {
-          // scone_i4_scale_slot: the lane's two group scales (segment 0: group lane / 16, segment 1: group 4 + lane / 16)
-          // are the two halves of ONE dword -- one load and one register per row instead of two
-          scw[k][s] = s == 0 ? reinterpret_cast<const uint32_t *>(scales_v)[lr * (D / SCONE_I4_GROUP / 2) + (lane >> 4)] : 0u;
-        } else {
-          scw[k][s] = reinterpret_cast<const unsigned short *>(scales_v)[lr * (D / SCONE_I4_GROUP) +
-                                                                         scone_i4_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_I4_GROUP, D)];
-        }
-      } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-        if constexpr (D == 1024) {
-          // scone_mx_scale_slot: the lane's two block scales (segment 0: block lane / 4, segment 1: block 16 + lane / 4) are
-          // the two bytes of ONE 16-bit word
-          scw[k][s] = s == 0 ? reinterpret_cast<const unsigned short *>(scales_v)[lr * (D / SCONE_MX_BLOCK / 2) + (lane >> 2)] : 0u;
-        } else {
-          scw[k][s] = reinterpret_cast<const uint8_t *>(scales_v)[lr * (D / SCONE_MX_BLOCK) +
-                                                                  scone_mx_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_MX_BLOCK, D)];
-        }
-      } else {
-        scw[k][s] = 0;
-      }
+      if constexpr (C::ROW_SCALE)  // one register per row, in slot 0
+        scw[k][s] = s == 0 ? C::row_pair_bits(scales_v, lr) : 0u;
+      else if constexpr (C::seg_pair(D))
+        scw[k][s] = s == 0 ? C::seg_pair_bits(scales_v, lr, lane) : 0u;
+      else
+        scw[k][s] = C::scale_bits(scales_v, lr, D, G::seg_first(s) + lane * G::seg_elems(s));
     }
   }
 
@@ -338,42 +268,35 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
 #pragma unroll
   for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
 #ifndef SCONE_PROBE_NO_MATH
-  if constexpr (FMT == SCONE_FMT_BF16 && K > 0) {  // column by column (bf16_accumulate_column); every other format: the loop below
+  if constexpr (C::BY_COLUMN && K > 0) {  // column by column (add_column); every other format: the loop below
 #pragma unroll
     for (int s = 0; s < NSEG; ++s) {
 #pragma unroll
       for (int i = 0; i < G::seg_row_words(s); ++i) {
-        const int a = G::seg_acc(s) + 2 * i;
-        bf16_accumulate_column<K, NWR>(&raw[0][G::seg_row_word0(s) + i], acc[a], acc[a + 1], a > 0 ? &acc[a - 2] : nullptr);
+        const int a = G::seg_acc(s) + C::EPW * i;
+        C::template add_column<K, NWR>(&raw[0][G::seg_row_word0(s) + i], &acc[a], a > 0 ? &acc[a - C::EPW] : nullptr);
       }
     }
   }
-  constexpr int KROWS = FMT == SCONE_FMT_BF16 ? 0 : K;
+  constexpr int KROWS = C::BY_COLUMN ? 0 : K;
 #else
   constexpr int KROWS = K;
 #endif
 #pragma unroll
   for (int k = 0; k < KROWS; ++k) {
     float sc0 = 1.0f;
-    if constexpr (FMT == SCONE_FMT_I8) {
+    if constexpr (C::ROW_SCALE) {
       const long long lr = (long long)rec[k] - row_begin;
-      sc0 = __half2float(__ushort_as_half((unsigned short)((lr & 1) ? (scw[k][0] >> 16) : (scw[k][0] & 0xFFFFu))));
+      sc0 = C::scale_operand(SCONE_SCALE_OF_PAIR(scw[k][0], lr & 1, C::SCALE_BITS));
     }
 #pragma unroll
     for (int s = 0; s < NSEG; ++s) {
       float sc = sc0;
-      if constexpr (FMT == SCONE_FMT_I4) {
-        if constexpr (D == 1024)
-          sc = __half2float(__ushort_as_half((unsigned short)(s == 0 ? (scw[k][0] & 0xFFFFu) : (scw[k][0] >> 16))));
-        else
-          sc = __half2float(__ushort_as_half((unsigned short)scw[k][s]));
-      } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-        if constexpr (D == 1024)
-          sc = mx_scale_operand(s == 0 ? (scw[k][0] & 0xFFu) : (scw[k][0] >> 8));
-        else
-          sc = mx_scale_operand(scw[k][s]);
-      }
-      // acc[seg_acc(s) ..] += dequant(raw[k][seg words]); exact products, list order (see accumulate<>)
+      if constexpr (C::seg_pair(D))
+        sc = C::scale_operand(SCONE_SCALE_OF_PAIR(scw[k][0], s != 0, C::SCALE_BITS));
+      else if constexpr (!C::ROW_SCALE)
+        sc = C::scale_operand(scw[k][s]);
+      // acc[seg_acc(s) ..] += dequant(raw[k][seg words]), list order (row_codec<>::add_word)
 #pragma unroll
       for (int i = 0; i < G::seg_row_words(s); ++i) {
         const uint32_t w = raw[k][G::seg_row_word0(s) + i];
@@ -381,27 +304,9 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
         acc[(G::seg_row_word0(s) + i) % EPL] = __uint_as_float(__float_as_uint(acc[(G::seg_row_word0(s) + i) % EPL]) ^ w ^ __float_as_uint(sc));
         continue;
 #endif
-        if constexpr (FMT == SCONE_FMT_F32) {
-          acc[G::seg_acc(s) + i] += __uint_as_float(w);
-        } else if constexpr (FMT == SCONE_FMT_F16) {
-          acc[G::seg_acc(s) + 2 * i] += __half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu)));
-          acc[G::seg_acc(s) + 2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w >> 16)));
-        } else if constexpr (FMT == SCONE_FMT_BF16) {
-          // (summed above, column by column: this loop has no iterations)
-        } else if constexpr (FMT == SCONE_FMT_I8) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const int q = (int)(w << (24 - 8 * b)) >> 24;
-            acc[G::seg_acc(s) + 4 * i + b] = fmaf(sc, (float)q, acc[G::seg_acc(s) + 4 * i + b]);
-          }
-        } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-          const int a = G::seg_acc(s) + 8 * i;  // the word summed before this one: the lane's previous 8 elements, or the last 8 of the row before
-          const int b = a > 0 ? a - 2 : EPL - 2;
-          mx_accumulate(w, sc, &acc[a], a > 0 || k > 0, acc[b], acc[b + 1]);
-        } else {
-          static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
-          i4_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
-        }
+        const int a = G::seg_acc(s) + C::EPW * i;  // the word summed before this one: the lane's previous elements, or the last of the row before
+        const int b = a > 0 ? a - 2 : EPL - 2;
+        C::add_word(w, sc, &acc[a], a > 0 || k > 0, acc[b], acc[b + 1]);
       }
     }
   }
@@ -417,7 +322,7 @@ __device__ __forceinline__ void embed_token(const scone_row_store &rows, const v
 #ifndef SCONE_PROBE_NO_MATH
   if (reduce == SCONE_REDUCE_MEAN && kfull > 1) {
     // engine.py:250: sum / K, the IEEE quotient for every sum (overflowed to inf, subnormal, NaN): scone_mean_div.h
-    mean_div<FMT>(acc, EPL, kfull);
+    C::mean_div(acc, EPL, kfull);
   }
 #endif
   uint32_t ow[NWO];
@@ -803,8 +708,8 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
                                             int reduce, const uint8_t *wte_row,  // (no __restrict__: out == base, see embed_token)
                                             const uint8_t *__restrict__ wpe_row, uint8_t *out_row, uint32_t lane) {
   constexpr int U = 8;                                  // elements per unit
-  static_assert(FMT >= SCONE_FMT_F32 && FMT <= SCONE_FMT_MXFP4, "unknown table format");
-  constexpr int RW = FMT == SCONE_FMT_F32 ? 8 : (FMT == SCONE_FMT_F16 || FMT == SCONE_FMT_BF16) ? 4 : FMT == SCONE_FMT_I8 ? 2 : 1;  // row words per unit (last arm: INT4 and MXFP4)
+  using C = row_codec<FMT>;
+  constexpr int RW = C::RW8;                            // row words per unit
   constexpr int OW = U * (int)sizeof(OutT) / 4;         // output words per unit
   constexpr int OPW = pack_io<OutT>::PER_WORD;
   constexpr int KK = K > 0 ? K : 1;
@@ -816,10 +721,10 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
   for (int k = 0; k < K; ++k) {
     lrs[k] = (long long)rec[k] - row_begin;
     rp[k] = rows.row((unsigned long long)lrs[k]);
-    sc8[k] = 1.0f;
-    if constexpr (FMT == SCONE_FMT_I8) {
-      const uint32_t w = reinterpret_cast<const uint32_t *>(scales_v)[lrs[k] >> 1];
-      sc8[k] = __half2float(__ushort_as_half((unsigned short)((lrs[k] & 1) ? (w >> 16) : (w & 0xFFFFu))));
+    sc8[k] = 1.0f;  // a per-row scale is fetched once, here; every other one per unit
+    if constexpr (C::ROW_SCALE) {
+      const uint32_t w = C::row_pair_bits(scales_v, lrs[k]);
+      sc8[k] = C::scale_operand(SCONE_SCALE_OF_PAIR(w, lrs[k] & 1, C::SCALE_BITS));
     }
   }
   const bool do_mean = reduce == SCONE_REDUCE_MEAN && kfull > 1;
@@ -839,46 +744,24 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
 #pragma unroll
       for (int i = 0; i < RW; ++i) raw[k][i] = p[i];
       scw[k] = 0;
-      if constexpr (FMT == SCONE_FMT_I4)
-        scw[k] = reinterpret_cast<const unsigned short *>(scales_v)[lrs[k] * (d / SCONE_I4_GROUP) + scone_i4_scale_slot((u * U) / SCONE_I4_GROUP, d)];
-      if constexpr (FMT == SCONE_FMT_MXFP4)
-        scw[k] = reinterpret_cast<const uint8_t *>(scales_v)[lrs[k] * (d / SCONE_MX_BLOCK) + scone_mx_scale_slot((u * U) / SCONE_MX_BLOCK, d)];
+      if constexpr (!C::ROW_SCALE) scw[k] = C::scale_bits(scales_v, lrs[k], d, u * U);
     }
     float acc[U];
 #pragma unroll
     for (int e = 0; e < U; ++e) acc[e] = 0.f;
-    if constexpr (FMT == SCONE_FMT_BF16 && K > 0) {  // column by column, as in embed_token
+    if constexpr (C::BY_COLUMN && K > 0) {  // column by column, as in embed_token
 #pragma unroll
       for (int i = 0; i < RW; ++i)
-        bf16_accumulate_column<K, RW>(&raw[0][i], acc[2 * i], acc[2 * i + 1], i > 0 ? &acc[2 * i - 2] : nullptr);
+        C::template add_column<K, RW>(&raw[0][i], &acc[C::EPW * i], i > 0 ? &acc[C::EPW * (i - 1)] : nullptr);
     }
 #pragma unroll
-    for (int k = 0; k < (FMT == SCONE_FMT_BF16 ? 0 : K); ++k) {
+    for (int k = 0; k < (C::BY_COLUMN ? 0 : K); ++k) {
       float sc = sc8[k];
-      if constexpr (FMT == SCONE_FMT_I4) sc = __half2float(__ushort_as_half((unsigned short)scw[k]));
-      if constexpr (FMT == SCONE_FMT_MXFP4) sc = mx_scale_operand(scw[k]);
+      if constexpr (!C::ROW_SCALE) sc = C::scale_operand(scw[k]);
 #pragma unroll
       for (int i = 0; i < RW; ++i) {
-        const uint32_t w = raw[k][i];
-        if constexpr (FMT == SCONE_FMT_F32) {
-          acc[i] += __uint_as_float(w);
-        } else if constexpr (FMT == SCONE_FMT_F16) {
-          acc[2 * i] += __half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu)));
-          acc[2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w >> 16)));
-        } else if constexpr (FMT == SCONE_FMT_BF16) {
-          // (summed above, column by column: this loop has no iterations)
-        } else if constexpr (FMT == SCONE_FMT_I8) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const int q = (int)(w << (24 - 8 * b)) >> 24;
-            acc[4 * i + b] = fmaf(sc, (float)q, acc[4 * i + b]);
-          }
-        } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-          mx_accumulate(w, sc, acc, k > 0, acc[6], acc[7]);
-        } else {
-          static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
-          i4_accumulate(w, sc, acc);
-        }
+        const int a = C::EPW * i, b = a > 0 ? a - 2 : U - 2;  // b: the word summed before this one, as in embed_token
+        C::add_word(raw[k][i], sc, &acc[a], a > 0 || k > 0, acc[b], acc[b + 1]);
       }
     }
     if constexpr (PARTIAL) {
@@ -886,7 +769,7 @@ __device__ __forceinline__ void embed_units(const scone_row_store &rows, const v
 #pragma unroll
       for (int e = 0; e < U; ++e) po[e] = __float_as_uint(acc[e]);
     } else {
-      if (do_mean) mean_div<FMT>(acc, U, kfull);  // IEEE x / K (scone_mean_div.h)
+      if (do_mean) C::mean_div(acc, U, kfull);  // IEEE x / K (scone_mean_div.h)
       uint32_t *po = reinterpret_cast<uint32_t *>(out_row) + (size_t)u * OW;
 #pragma unroll
       for (int w = 0; w < OW; ++w) {
@@ -1002,6 +885,7 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
                                                  int reduce, const uint8_t *__restrict__ base_row, uint8_t *__restrict__ out_row,
                                                  uint32_t lane) {
   using G = wave_geom<FMT, D>;
+  using C = row_codec<FMT>;
   constexpr int EPL = G::EPL, NSEG = G::NSEG;
   constexpr int NWO = EPL * (int)sizeof(OutT) / 4;
   constexpr int OPW = pack_io<OutT>::PER_WORD;
@@ -1019,43 +903,12 @@ __device__ __forceinline__ void embed_token_long(const scone_row_store &rows, co
     for (int s = 0; s < NSEG; ++s) {
       const uint32_t *p = reinterpret_cast<const uint32_t *>(rp + G::seg_first(s) / 4 * G::BPE4 +
                                                               lane * (uint32_t)(G::seg_elems(s) * G::BPE4 / 4));
-      float sc = 1.0f;
-      if constexpr (FMT == SCONE_FMT_I8) {
-        sc = __half2float(reinterpret_cast<const __half *>(scales_v)[lr]);
-      } else if constexpr (FMT == SCONE_FMT_I4) {
-        sc = __half2float(reinterpret_cast<const __half *>(scales_v)[lr * (D / SCONE_I4_GROUP) +
-                                                                      scone_i4_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_I4_GROUP, D)]);
-      } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-        sc = mx_scale_operand(reinterpret_cast<const uint8_t *>(scales_v)[lr * (D / SCONE_MX_BLOCK) +
-                                                                          scone_mx_scale_slot((G::seg_first(s) + lane * G::seg_elems(s)) / SCONE_MX_BLOCK, D)]);
-      }
+      const float sc = C::scale_operand(C::scale_bits(scales_v, lr, D, G::seg_first(s) + lane * G::seg_elems(s)));
 #pragma unroll
-      for (int i = 0; i < G::seg_row_words(s); ++i) {
-        const uint32_t w = p[i];
-        if constexpr (FMT == SCONE_FMT_F32) {
-          acc[G::seg_acc(s) + i] += __uint_as_float(w);
-        } else if constexpr (FMT == SCONE_FMT_F16) {
-          acc[G::seg_acc(s) + 2 * i] += __half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu)));
-          acc[G::seg_acc(s) + 2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w >> 16)));
-        } else if constexpr (FMT == SCONE_FMT_BF16) {
-          acc[G::seg_acc(s) + 2 * i] += __uint_as_float(w << 16);  // a bf16 is the upper half of its fp32
-          acc[G::seg_acc(s) + 2 * i + 1] += __uint_as_float(w & 0xFFFF0000u);
-        } else if constexpr (FMT == SCONE_FMT_I8) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const int q = (int)(w << (24 - 8 * b)) >> 24;
-            acc[G::seg_acc(s) + 4 * i + b] = fmaf(sc, (float)q, acc[G::seg_acc(s) + 4 * i + b]);
-          }
-        } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-          mx_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
-        } else {
-          static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
-          i4_accumulate(w, sc, &acc[G::seg_acc(s) + 8 * i]);
-        }
-      }
+      for (int i = 0; i < G::seg_row_words(s); ++i) C::add_word(p[i], sc, &acc[G::seg_acc(s) + C::EPW * i]);
     }
   }
-  if (reduce == SCONE_REDUCE_MEAN && K > 1) mean_div<FMT>(acc, EPL, K);  // IEEE x / K for any list length (scone_mean_div.h)
+  if (reduce == SCONE_REDUCE_MEAN && K > 1) C::mean_div(acc, EPL, K);  // IEEE x / K for any list length (scone_mean_div.h)
   uint32_t ow[NWO];
 #pragma unroll
   for (int w = 0; w < NWO; ++w) {
@@ -1283,7 +1136,7 @@ int launch_table_fmt(scone_handle *h, const embed_args &a, int src, int mode, in
     return rc != -1 ? rc : launch_dtype<FMT, SRC_HITS, MODE_PARTIAL>(h, a, out_dtype, s);
   }
   if (mode == MODE_FINALIZE) {
-    if constexpr (FMT == SCONE_FMT_F32) {
+    if constexpr (row_codec<FMT>::PLAIN_F32) {  // the partial sums have an fp32 table's layout
       int rc = -1;
       switch (out_dtype) {
         case SCONE_DT_F32: rc = try_launch_finalize_wave<float>(h, a, s); break;

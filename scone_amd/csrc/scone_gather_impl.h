@@ -17,19 +17,11 @@
 // on the launch geometry.
 #pragma once
 #include "scone_common.h"
+#include "scone_row_codec.h"
 
 #include <type_traits>
 
 namespace scone_gather {
-
-
-template <int FMT> struct fmt_traits;
-template <> struct fmt_traits<SCONE_FMT_F32> { static constexpr int VEC = 4; };
-template <> struct fmt_traits<SCONE_FMT_F16> { static constexpr int VEC = 8; };
-template <> struct fmt_traits<SCONE_FMT_I8> { static constexpr int VEC = 16; };
-template <> struct fmt_traits<SCONE_FMT_I4> { static constexpr int VEC = 32; };
-template <> struct fmt_traits<SCONE_FMT_BF16> { static constexpr int VEC = 8; };
-template <> struct fmt_traits<SCONE_FMT_MXFP4> { static constexpr int VEC = 32; };  // 16 B = one block of 32 elements
 
 struct table_view {
   scone_row_store st;    // payload rows (local): HBM part + pinned-host part
@@ -96,92 +88,18 @@ __device__ __forceinline__ void store_vec(T *__restrict__ p, const float (&v)[N]
   }
 }
 
-// MXFP4: acc[0..8) += the 8 E2M1 elements of payload dword w (element 2k = low nibble of byte k) times the block scale, with
-// gfx950's packed convert: v_cvt_scalef32_pk_f32_fp4 turns the two nibbles of byte `byte_sel` into two fp32 and applies the
-// scale operand's exponent -- two elements per VALU instruction, then one add each.  `sc` is mx_scale_operand(X): the E8M0
-// byte in an fp32 exponent field.  The product is exact wherever it is finite, so acc += value is the oracle's sum of the
-// dequantised table; the exhaustive (code, X) test of tests/test_gpu_mxfp4_table.py holds the convert to the definition.
-// `tie`: p0, p1 are two accumulators of the word summed just before this one.  A convert has no operand but the loaded word and
-// its scale, so left to itself the scheduler decodes every row as it arrives -- 8 fp32 per payload dword in flight, and the
-// K >= 4 paths of k_embed_wave spill (fp32 output, d = 1024, max_n = 4: 164 B of scratch).  The empty asm emits nothing; it
-// makes every convert wait for the two sums written just before it (the previous byte's; for the first byte, with `tie`, the
-// previous word's), as bf16_accumulate_column does for bf16: rows stay packed until they are summed.
-__device__ __forceinline__ float mx_scale_operand(uint32_t x) { return __uint_as_float(x << 23); }
-__device__ __forceinline__ void mx_accumulate(uint32_t w, float sc, float *acc, bool tie = false, float p0 = 0.f, float p1 = 0.f) {
-  typedef float mx_f2 __attribute__((ext_vector_type(2)));
-  if (tie) asm("" : "+v"(w) : "v"(p0), "v"(p1));
-  const mx_f2 v0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 0);
-  acc[0] += v0.x, acc[1] += v0.y;
-  asm("" : "+v"(w) : "v"(acc[0]), "v"(acc[1]));
-  const mx_f2 v1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 1);
-  acc[2] += v1.x, acc[3] += v1.y;
-  asm("" : "+v"(w) : "v"(acc[2]), "v"(acc[3]));
-  const mx_f2 v2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 2);
-  acc[4] += v2.x, acc[5] += v2.y;
-  asm("" : "+v"(w) : "v"(acc[4]), "v"(acc[5]));
-  const mx_f2 v3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 3);
-  acc[6] += v3.x, acc[7] += v3.y;
-}
-
-// acc[0..VEC) += dequant(raw); the products scale*q are exact in fp32 (11-bit x 8-bit
-// significands), so fmaf(scale, q, acc) == acc + fp32(scale*q): the same value the
-// oracle adds when it sums the dequantised fp32 table.
+// acc[0..VEC) += dequant(raw): the four words of a lane's 16-byte vector, one scale for all of them
 template <int FMT>
-__device__ __forceinline__ void accumulate(float (&acc)[fmt_traits<FMT>::VEC], const uint4 &raw, float scale) {
+__device__ __forceinline__ void accumulate(float (&acc)[row_codec<FMT>::VEC], const uint4 &raw, float scale) {
   const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-  if constexpr (FMT == SCONE_FMT_F32) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] += __uint_as_float(w[i]);
-  } else if constexpr (FMT == SCONE_FMT_F16) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[2 * i] += __half2float(__ushort_as_half((unsigned short)(w[i] & 0xFFFFu)));
-      acc[2 * i + 1] += __half2float(__ushort_as_half((unsigned short)(w[i] >> 16)));
-    }
-  } else if constexpr (FMT == SCONE_FMT_BF16) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {  // a bf16 is the upper half of its fp32: bits << 16
-      acc[2 * i] += __uint_as_float(w[i] << 16);
-      acc[2 * i + 1] += __uint_as_float(w[i] & 0xFFFF0000u);
-    }
-  } else if constexpr (FMT == SCONE_FMT_I8) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int q = (int)(w[i] << (24 - 8 * b)) >> 24;  // sign-extended byte b
-        acc[4 * i + b] = fmaf(scale, (float)q, acc[4 * i + b]);
-      }
-    }
-  } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mx_accumulate(w[i], scale, &acc[8 * i]);  // scale: mx_scale_operand of the vector's block
-  } else {
-    static_assert(FMT == SCONE_FMT_I4, "every table format has its own branch");
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        const int q = (int)((w[i] >> (4 * b)) & 0xFu) - 8;
-        acc[8 * i + b] = fmaf(scale, (float)q, acc[8 * i + b]);
-      }
-    }
-  }
+  for (int i = 0; i < 4; ++i) row_codec<FMT>::add_word(w[i], scale, &acc[row_codec<FMT>::EPW * i]);
 }
 
+// the scale operand of vector v (elements v * VEC ...) of local row lr; 1 for a format without scales
 template <int FMT>
 __device__ __forceinline__ float load_scale(const table_view &tv, long long lr, int v) {
-  if constexpr (FMT == SCONE_FMT_I8) {
-    return __half2float(tv.scales[lr]);
-  } else if constexpr (FMT == SCONE_FMT_I4) {
-    // 32 elements per vector, 128 per group -> 4 vectors share a scale
-    return __half2float(tv.scales[lr * (long long)(tv.d / SCONE_I4_GROUP) + scone_i4_scale_slot(v >> 2, tv.d)]);
-  } else if constexpr (FMT == SCONE_FMT_MXFP4) {
-    // 32 elements per vector = one block: vector v has its own scale byte
-    return mx_scale_operand(reinterpret_cast<const uint8_t *>(tv.scales)[lr * (long long)(tv.d / SCONE_MX_BLOCK) + scone_mx_scale_slot(v, tv.d)]);
-  } else {
-    return 1.0f;
-  }
+  return row_codec<FMT>::scale_operand(row_codec<FMT>::scale_bits(tv.scales, lr, tv.d, v * row_codec<FMT>::VEC));
 }
 
 // candidate c -> (n, s): n = 1..max_n, s = n-1..0 (window start ascending)
@@ -239,7 +157,7 @@ enum { MODE_FULL = 0, MODE_PARTIAL = 1, MODE_FINALIZE = 2 };
 // compiled max_n bound for the hit source).
 template <int FMT, typename OutT, int D, int LPT, int NCAND, int SRC, int MODE>
 __global__ __launch_bounds__(256) void k_embed(const embed_args a) {
-  constexpr int VEC = fmt_traits<FMT>::VEC;
+  constexpr int VEC = row_codec<FMT>::VEC;
   constexpr int GROUPS = 64 / LPT;
   constexpr int UNROLL = D ? (D / VEC + LPT - 1) / LPT : 1;
   static_assert(NCAND <= LPT, "one candidate per lane of the group");
@@ -407,7 +325,7 @@ int launch_one(scone_handle *h, const embed_args &a, hipStream_t s) {
 // geometry table: lanes per token for the specialised dims; other dims take the runtime-d kernel
 template <int FMT, typename OutT, int NCAND, int SRC, int MODE>
 int launch_dim(scone_handle *h, const embed_args &a, hipStream_t s) {
-  constexpr int VEC = fmt_traits<FMT>::VEC;
+  constexpr int VEC = row_codec<FMT>::VEC;
   const int d = a.tv.d;
   if (d == 768 && (768 / VEC) % 16 == 0) return launch_one<FMT, OutT, 768, 16, NCAND, SRC, MODE>(h, a, s);
   if (d == 1024 && (1024 / VEC) % 16 == 0) return launch_one<FMT, OutT, 1024, 16, NCAND, SRC, MODE>(h, a, s);

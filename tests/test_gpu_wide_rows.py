@@ -516,3 +516,84 @@ def test_eviction_of_cached_rows_with_scales(fmt, d):
             assert c["rows_copied"] > copied                             # the second pass misses again
         copied = c["rows_copied"]
     assert t.status() == 0
+
+
+# ------------------------------------------------------------------ every format through each of the four row-decoding bodies
+# The narrow end, in the file that has the helpers: (format, d) x the body that decodes the rows there.
+#   d = 768 (two segments, the second of 256 elements), 1024 (INT4 / MXFP4: the packed scale pair), 1280 (three segments):
+#       embed_token under k_embed_wave (hit lists) and under k_embed_csr_wave (caller's lists up to 10 owned ids),
+#       embed_token_long (caller's lists of 11 and 23 ids)
+#   d = 520 (65 units: lane 0 walks two), int8 528 (d % 16 == 0), INT4 / MXFP4 640 (d % 128 == 0): embed_units under k_embed_wave_any, and the
+#       lane-group k_embed for the caller's lists.  INT4 / MXFP4 take these two at 768 and 1280 as well (a trailing segment of
+#       256 elements would be 2 row bytes per lane: wave_geom<>::OK is false), which is three more widths for the one kernel
+#       whose INT4 decode is shared with the wave bodies, k_embed
+# Lists of 0, 1, 6 (all candidates at max_n = 3), 10 (at max_n = 4), 11 and 23 ids, mean and sum, 64 tokens at the most.
+NARROW_FMTS = ("fp32", "fp16", "bf16", "int8", "int4", "mxfp4")
+NARROW_UNITS = {"int8": 528, "int4": 640, "mxfp4": 640}          # the smallest width of more than 64 units scone_create accepts; else 520
+NARROW = [pytest.param(f, d, id=f"{f}-d{d}") for f in NARROW_FMTS for d in (768, 1024, 1280, NARROW_UNITS.get(f, 520))]
+NARROW_MAX_N = 4
+NARROW_KS = (0, 1, 6, 10, 11, 23, 3, 0)
+
+
+def _narrow_tables(fmt, d):
+    rng = np.random.default_rng(13 * d + NARROW_FMTS.index(fmt))
+    n = W.N_ROWS[NARROW_MAX_N]
+    table = (rng.standard_normal((n, d)) * F._magnitudes(rng, n, d)).astype(np.float32)
+    wte = rng.standard_normal((F.VOCAB + 1, d)).astype(np.float32)
+    wpe = rng.standard_normal((F.N_POS, d)).astype(np.float32)
+    return table, F.quantise(fmt, table)[2], wte, wpe
+
+
+def _narrow_batch(max_n):
+    """tok [4, 16]: the first seed at which the list lengths 0, 1 and max_n (max_n + 1) / 2 all occur."""
+    keys, lens = W._vocabulary(max_n)
+    full = max_n * (max_n + 1) // 2
+    for seed in range(9000, 9400):
+        tok = np.random.default_rng(seed).choice(F.VOCAB + 1, size=(4, 16), p=W.TOKEN_P).astype(np.int64)
+        hist = np.bincount(F.list_lengths(keys, lens, tok, max_n), minlength=full + 1)
+        if hist[0] and hist[1] and hist[full]:
+            return keys, lens, tok
+    raise AssertionError(f"no seed gives the list lengths 0, 1 and {full}")
+
+
+@pytest.mark.parametrize("fmt,d", NARROW)
+def test_every_format_through_every_row_decoding_body(fmt, d):
+    from scone_amd.hip_backend import SconeTable
+    table, stored, wte, wpe = _narrow_tables(fmt, d)
+    n = len(table)
+    token_body = d in (768, 1024, 1280) and not (fmt in ("int4", "mxfp4") and d != 1024)
+    assert F.kernel_family(fmt, d) == ("k_embed_wave" if token_body else "k_embed_wave_any")
+    # hit lists, two kernels: embed_token / embed_units
+    for max_n in (3, NARROW_MAX_N):
+        keys, lens, tok = _narrow_batch(max_n)
+        m = len(lens)
+        t = SconeTable(max_n, m, d, fmt)
+        t.index_build(keys, lens)
+        t.store_f32(torch.from_numpy(table[:m]))
+        wte_t, wpe_t = _dev(wte, torch.float32), _dev(wpe, torch.float32)
+        for reduce in ("mean", "sum"):
+            out = _embed(t, tok, torch.float32, reduce=reduce, wte=wte_t, wpe=wpe_t)
+            want = F.want(stored[:m], tok, reduce, "cover", wte, wpe, vocab=(keys, lens, max_n))
+            _same(out, want, torch.float32, (fmt, d, max_n, reduce, "hit lists"))
+        assert t.status() == 0
+    # the caller's lists: embed_token and embed_token_long under k_embed_csr_wave / the lane-group k_embed
+    keys, lens = W._vocabulary(NARROW_MAX_N)
+    rng = np.random.default_rng(17 * d)
+    off = np.zeros(len(NARROW_KS) + 1, dtype=np.int64)
+    np.cumsum(NARROW_KS, out=off[1:])
+    ids = rng.integers(0, n, size=int(off[-1])).astype(np.int64)
+    base = rng.standard_normal((len(NARROW_KS), d)).astype(np.float32)
+    kf = np.asarray(NARROW_KS, dtype=np.float32)[:, None]
+    for lo in (0, 20):
+        t = SconeTable(NARROW_MAX_N, n, d, fmt, row_begin=lo, row_end=n)
+        t.index_build(keys, lens)
+        t.store_f32(torch.from_numpy(table[lo:]), row0=lo)
+        sums, kown = W._own_sums(stored, off, ids, lo, n)
+        assert lo == 0 or ((kown < np.asarray(NARROW_KS)).any() and kown.max() > 10)
+        mean = np.where(kf > 1, sums / np.maximum(kf, np.float32(1)), sums).astype(np.float32)
+        for reduce, fg in (("sum", sums), ("mean", mean)):
+            out = t.gather_reduce(torch.from_numpy(off), torch.from_numpy(ids), reduce, out_dtype=torch.float32)
+            _same(out, fg, torch.float32, (fmt, d, lo, reduce, "lists"))
+            out = t.gather_reduce(torch.from_numpy(off), torch.from_numpy(ids), reduce, base=torch.from_numpy(base), out_dtype=torch.float32)
+            _same(out, base + fg, torch.float32, (fmt, d, lo, reduce, "lists + base"))
+        assert t.status() == 0

@@ -6,7 +6,7 @@
 # the occupancy estimate of scone_embed_wave.h accounted for its scale registers).  CPU only (hipcc -S).
 cd "$(dirname "$0")/../scone_amd/csrc" || exit 1
 rc=0
-for src in scone_gather_i8 scone_gather_i4 scone_gather_f16 scone_gather_f32 scone_index \
+for src in scone_gather_i8 scone_gather_i4 scone_gather_f16 scone_gather_f32 scone_gather_bf16 scone_gather_mxfp4 scone_index \
            scone_select_f32 scone_select_f16 scone_select_i8 scone_select_i4 scone_select_bf16 scone_select_mxfp4 scone_backward scone_backward_apply scone_opt scone_opt_lean; do
   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off --cuda-device-only -S $src.hip -o /tmp/$src.s 2>/dev/null || { echo "compile failed: $src"; exit 1; }
   python3 - /tmp/$src.s $src <<'PY' || rc=1
