@@ -857,6 +857,70 @@ int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_
 int scone_backward_apply_lean(scone_handle *h, scone_bwd_plan *plan, const void *d_grad_out, int32_t grad_dtype, int32_t reduce,
                               const scone_lean_cfg *cfg, float *d_row_state, scone_stream_t stream);
 
+/* ---- gradient norm, clipping and skipped steps: what a training loop puts around the optimizer step, kept on the device (new
+ * here; torch.nn.utils.clip_grad_norm_ cannot take a sparse gradient, and a GradScaler's found-inf check is a host read).
+ * Appended: SCONE_ABI_VERSION is unchanged and every entry point above keeps its bits and its behaviour.  Three parts:
+ * scone_grad_sqnorm reduces d_grad_rows to its squared norm in a fixed order; scone_grad_ctl_set turns such terms into a clip
+ * coefficient and a skip flag in a 24-byte block on the device; scone_opt_step_ctl / scone_opt_step_lean_ctl are the two
+ * optimizer steps reading their scale and the flag from that block.  No call synchronises or allocates; all are stream-ordered.
+ *
+ * 1. scone_grad_sqnorm.  d_grad_rows is fp32 [n, d], d = cfg.dim (a multiple of 4), what scone_backward_rows returns.
+ *   d_scratch holds scone_grad_sqnorm_scratch(n) = n + ceil(n / 1024) doubles (that call does no device work); d_sq_out is ONE
+ *   double.  All sums are IEEE double, every addition rounded once.  Element g enters as (double)g * (double)g: that product is
+ *   exact (48 significant bits), so fusing it with the addition cannot change a bit.  Every fp32 value, its square and any sum
+ *   of them fit a double: the total is finite if and only if every element is finite, and it is exactly +0.0 only if every
+ *   element is +-0 (subnormal elements count).
+ *   Row r (the lane order of the lean step's row sum).  Element j of the row belongs to lane l = (j / 4) % 64.  a_l = +0.0; then
+ *     a_l = a_l + g_j * g_j in ascending j (a lane with no element keeps +0.0).  Then, for s = 32, 16, 8, 4, 2, 1:
+ *     a_l = a_l + a_(l ^ s), all 64 lanes at once.  Q_r = a_0 is stored to d_scratch[r]: the per-row squared norms are an output.
+ *   Tile k covers rows [1024k, 1024k + 1024).  Thread t of 256 starts at b_t = +0.0 and adds Q_(1024k + t + 256i) for i = 0, 1,
+ *     2, 3 in that order, skipping rows >= n.  Then a tree, for s = 128, 64, .. 1: b_t = b_t + b_(t + s) for every t < s.
+ *     P_k = b_0 is stored to d_scratch[n + k]; there are ceil(n / 1024) tiles.
+ *   Total.  One workgroup of 256 threads: thread t starts at +0.0 and adds P_(t + 256i) in ascending i; the same tree follows;
+ *     b_0 is stored to *d_sq_out.  n == 0 stores +0.0 (no tile, nothing else is written or read).
+ *   The result is a pure function of the n * d input values: it does not depend on the grid, on SCONE_OPT_MAX_BLOCKS (which caps
+ *   the row kernel's grid as it caps scone_opt_step's) or on the run.  No atomics.  At most three kernel launches.
+ *   SCONE_EINVAL (scone_last_error names the reason, prefixed "scone_grad_sqnorm: "): a null d_grad_rows or d_scratch with
+ *   n > 0, a null d_sq_out, a handle with dim == 0.
+ *
+ * 2. scone_grad_ctl_set.  d_terms: n_terms (1 .. 64) doubles on the device -- the table's squared norm is one, the squared norm
+ *   of the dense parameters' gradients (the caller's, from torch) another, other shards one each.  ONE device thread computes,
+ *   every operation in IEEE double and rounded once, sqrt and / correctly rounded:
+ *     total  = +0.0; total = total + d_terms[i] in ascending i
+ *     norm64 = sqrt(total) * fabs(grad_scale)                  (the norm of the UN-scaled gradient)
+ *     c      = max_norm / (norm64 + 1e-6)                      (torch.nn.utils.clip_grad_norm_)
+ *     coef   = c < 1.0 ? (float)c : 1.0f                       (a NaN compares false: 1.0f)
+ *     skip   = skip_nonfinite != 0 && total is inf or NaN ? 1 : 0
+ *     sqnorm = total, norm = (float)norm64, reserved = 0
+ *   and stores the block to d_ctl.  max_norm = +inf: no clipping (coef = 1.0f).  One kernel launch.
+ *   SCONE_EINVAL (prefixed "scone_grad_ctl_set: "): a null d_terms / d_ctl, n_terms outside 1 .. 64, a grad_scale that is not
+ *   finite, a max_norm that is <= 0 or NaN.
+ *
+ * 3. scone_opt_step_ctl / scone_opt_step_lean_ctl: scone_opt_step / scone_opt_step_lean with d_ctl before the stream.  Every
+ *   wavefront reads skip and coef before it touches anything else.  skip != 0: the launch changes NOTHING -- no master or table
+ *   row, no state, no scale, no status bit (ids are not looked at).  Otherwise gscale_eff = gscale * coef, ONE fp32 product of
+ *   the cfg's gscale (scone_opt_scalars_of / scone_lean_scalars_of) and the block's coef, and the call is bit for bit the plain
+ *   call whose gscale is that value -- the exact skip of the multiply when gscale_eff == 1 included.  Still one launch, no
+ *   synchronisation, no allocation; ids, modes, formats and refusals are the plain call's (the host side cannot know the flag:
+ *   a staged-prefetch cache is dropped either way).  A null d_ctl: SCONE_EINVAL.  Messages are prefixed with the call's name.
+ *   scone_backward_apply_lean has no such form: a clipped update needs the norm before the first row is written. */
+typedef struct scone_grad_ctl {
+  double sqnorm;     /* the sum of the terms */
+  float norm;        /* sqrt(sqnorm) * |grad_scale| */
+  float coef;        /* min(1, max_norm / (norm + 1e-6)): multiply every gradient by it */
+  uint32_t skip;     /* 1: the _ctl steps change nothing */
+  uint32_t reserved; /* 0 */
+} scone_grad_ctl;    /* 24 bytes */
+int scone_grad_sqnorm_scratch(uint64_t n, uint64_t *n_doubles);
+int scone_grad_sqnorm(scone_handle *h, const float *d_grad_rows, uint64_t n, double *d_scratch, double *d_sq_out,
+                      scone_stream_t stream);
+int scone_grad_ctl_set(scone_handle *h, const double *d_terms, int32_t n_terms, double grad_scale, double max_norm,
+                       int32_t skip_nonfinite, scone_grad_ctl *d_ctl, scone_stream_t stream);
+int scone_opt_step_ctl(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
+                       float *d_master, float *d_state1, float *d_state2, const scone_grad_ctl *d_ctl, scone_stream_t stream);
+int scone_opt_step_lean_ctl(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                            uint64_t n, float *d_master, float *d_row_state, const scone_grad_ctl *d_ctl, scone_stream_t stream);
+
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
  * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.

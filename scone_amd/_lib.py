@@ -89,8 +89,28 @@ class LeanCfg(C.Structure):
     ]
 
 
+class SconeGradCtl(C.Structure):
+    """``scone_grad_ctl``: the 24 device bytes ``scone_grad_ctl_set`` writes and the ``_ctl`` optimizer steps read."""
+    _fields_ = [
+        ("sqnorm", C.c_double),
+        ("norm", C.c_float),
+        ("coef", C.c_float),
+        ("skip", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 _P = C.c_void_p
 _I32, _I64, _U32, _U64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
+
+
+def grad_sqnorm_scratch(n: int) -> int:
+    """``scone_grad_sqnorm_scratch``: the doubles ``scone_grad_sqnorm`` needs as scratch for ``n`` rows.  Runs without a GPU."""
+    out = _U64(0)
+    if lib().scone_grad_sqnorm_scratch(int(n), C.byref(out)) != OK:
+        raise ValueError("scone_grad_sqnorm_scratch refused its arguments")
+    return int(out.value)
+
 
 # name -> (restype, argtypes); must list every symbol include/scone_hip.h declares
 SIGNATURES = {
@@ -194,6 +214,11 @@ SIGNATURES = {
     "scone_lean_rand16": (_U32, [_U64, _I64, _U64, _U32]),
     "scone_opt_step_lean": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _U64, _P, _P, _P]),
     "scone_backward_apply_lean": (C.c_int, [_P, _P, _P, _I32, _I32, C.POINTER(LeanCfg), _P, _P]),
+    "scone_grad_sqnorm_scratch": (C.c_int, [_U64, C.POINTER(_U64)]),
+    "scone_grad_sqnorm": (C.c_int, [_P, _P, _U64, _P, _P, _P]),
+    "scone_grad_ctl_set": (C.c_int, [_P, _P, _I32, C.c_double, C.c_double, _I32, _P, _P]),
+    "scone_opt_step_ctl": (C.c_int, [_P, C.POINTER(OptCfg), _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "scone_opt_step_lean_ctl": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _U64, _P, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

@@ -58,7 +58,13 @@ __global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ id
                                                   unsigned long long n, unsigned long long row_begin, unsigned long long row_end,
                                                   int d, scone_opt_scalars sc, float *__restrict__ master, float *__restrict__ state1,
                                                   float *__restrict__ state2, scone_row_store st, __half *__restrict__ scales,
-                                                  uint32_t *__restrict__ status) {
+                                                  uint32_t *__restrict__ status, const scone_grad_ctl *__restrict__ ctl) {
+  // scone_opt_step_ctl (ctl != null; wave-uniform): a set skip flag ends the wave before it touches anything; else the block's
+  // coef joins gscale by one fp32 product and the rest is the plain call with that gscale
+  if (ctl) {
+    if (ctl->skip != 0u) return;
+    sc.gscale = opt_uniform(sc.gscale * ctl->coef);
+  }
   constexpr bool HAS_M = KIND == SCONE_OPT_ADAM;
   constexpr bool HAS_V = KIND != SCONE_OPT_SGD;
   const int lane = threadIdx.x & 63;
@@ -152,13 +158,14 @@ struct opt_args {
   unsigned long long n;
   scone_opt_scalars sc;
   float *master, *s1, *s2;
+  const scone_grad_ctl *ctl;  // null: scone_opt_step
 };
 
 template <int FMT, int KIND>
 void opt_launch(scone_handle *h, const opt_args &a, unsigned blocks, hipStream_t s) {
   hipLaunchKernelGGL((k_opt_step<FMT, KIND>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, a.n, (unsigned long long)h->cfg.row_begin,
                      (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2, scone_store_of(h),
-                     (__half *)h->scales, h->d_status);
+                     (__half *)h->scales, h->d_status, a.ctl);
 }
 
 template <int FMT>
@@ -179,21 +186,37 @@ extern "C" int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars 
   return SCONE_OK;
 }
 
-extern "C" int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
-                              float *d_master, float *d_state1, float *d_state2, scone_stream_t stream) {
-  const char *who = "scone_opt_step";
+namespace {
+
+// scone_opt_step (with_ctl false, ctl null) and scone_opt_step_ctl
+int opt_step(scone_handle *h, const char *who, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
+             float *d_master, float *d_state1, float *d_state2, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream) {
   SCONE_TRY(opt_need_table(h, who, opt_check(cfg)));
+  if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
   if (n == 0) return SCONE_OK;
   if (!d_row_ids || !d_grad_rows || !d_master) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
   if (cfg->kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, who, "Adam needs d_state1 (m)");
   if (cfg->kind != SCONE_OPT_SGD && !d_state2) return scone_refuse(h, SCONE_EINVAL, who, "Adam / Adagrad need d_state2 (v / the sum of squares)");
   SCONE_ON_DEVICE(h);
   opt_args a;
-  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2;
+  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2, a.ctl = d_ctl;
   opt_scalars(cfg, &a.sc);
   const unsigned blocks = opt_begin(h, n);
   const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch_kind<decltype(F)::value>(h, cfg->kind, a, blocks, (hipStream_t)stream); });
   if (bad) return scone_refuse(h, SCONE_EINVAL, who, "bad format");
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
+}
+
+}  // namespace
+
+extern "C" int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
+                              float *d_master, float *d_state1, float *d_state2, scone_stream_t stream) {
+  return opt_step(h, "scone_opt_step", cfg, d_row_ids, d_grad_rows, n, d_master, d_state1, d_state2, false, nullptr, stream);
+}
+
+extern "C" int scone_opt_step_ctl(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                                  uint64_t n, float *d_master, float *d_state1, float *d_state2, const scone_grad_ctl *d_ctl,
+                                  scone_stream_t stream) {
+  return opt_step(h, "scone_opt_step_ctl", cfg, d_row_ids, d_grad_rows, n, d_master, d_state1, d_state2, true, d_ctl, stream);
 }

@@ -22,7 +22,13 @@ __global__ __launch_bounds__(256) void k_opt_lean(const int64_t *__restrict__ id
                                                   unsigned long long n, unsigned long long row_begin, unsigned long long row_end,
                                                   int d, scone_opt_scalars sc, lean_rand rnd, float *__restrict__ master,
                                                   float *__restrict__ row_state, scone_row_store st, __half *__restrict__ scales,
-                                                  uint32_t *__restrict__ status) {
+                                                  uint32_t *__restrict__ status, const scone_grad_ctl *__restrict__ ctl) {
+  // scone_opt_step_lean_ctl (ctl != null; wave-uniform): as in k_opt_step -- a set skip flag ends the wave before it touches
+  // anything; else the block's coef joins gscale by one fp32 product
+  if (ctl) {
+    if (ctl->skip != 0u) return;
+    sc.gscale = opt_uniform(sc.gscale * ctl->coef);
+  }
   static_assert(!INPLACE || FMT == SCONE_FMT_F32 || FMT == SCONE_FMT_BF16, "only fp32 and bf16 rows are weights in place");
   static_assert(!STOCH || (INPLACE && FMT == SCONE_FMT_BF16), "only an in-place bf16 row is rounded");
   constexpr bool ROWWISE = KIND == SCONE_LEAN_ROWWISE_ADAGRAD;
@@ -139,13 +145,14 @@ struct lean_args {
   scone_opt_scalars sc;
   lean_rand rnd;
   float *master, *row_state;
+  const scone_grad_ctl *ctl;  // null: scone_opt_step_lean
 };
 
 template <int FMT, int KIND, bool INPLACE, bool STOCH>
 void lean_launch(scone_handle *h, const lean_args &a, unsigned blocks, hipStream_t s) {
   hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, a.n,
                      (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.rnd, a.master,
-                     a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status);
+                     a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
 }
 
 template <int FMT, bool INPLACE, bool STOCH>
@@ -168,10 +175,13 @@ extern "C" uint32_t scone_lean_rand16(uint64_t seed, int64_t step, uint64_t row_
   return scone_lean_rand16_of(scone_lean_row_key(seed, step, row_id), col);
 }
 
-extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
-                                   uint64_t n, float *d_master, float *d_row_state, scone_stream_t stream) {
-  const char *who = "scone_opt_step_lean";
+namespace {
+
+// scone_opt_step_lean (with_ctl false, ctl null) and scone_opt_step_lean_ctl
+int opt_step_lean(scone_handle *h, const char *who, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                  uint64_t n, float *d_master, float *d_row_state, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream) {
   SCONE_TRY(opt_need_table(h, who, lean_check(cfg)));
+  if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
   const int fmt = h->cfg.table_fmt;
   const bool inplace = d_master == nullptr, stoch = cfg->rounding == SCONE_ROUND_STOCHASTIC;
   if (inplace && fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
@@ -187,7 +197,7 @@ extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, c
     return scone_refuse(h, SCONE_EINVAL, who, "row-wise Adagrad needs d_row_state (one fp32 per owned row)");
   SCONE_ON_DEVICE(h);
   lean_args a;
-  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state;
+  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state, a.ctl = d_ctl;
   a.rnd.seed = cfg->seed, a.rnd.step = cfg->step;
   lean_scalars(cfg, &a.sc);
   const unsigned blocks = opt_begin(h, n);
@@ -204,4 +214,17 @@ extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, c
   }
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
+}
+
+}  // namespace
+
+extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                                   uint64_t n, float *d_master, float *d_row_state, scone_stream_t stream) {
+  return opt_step_lean(h, "scone_opt_step_lean", cfg, d_row_ids, d_grad_rows, n, d_master, d_row_state, false, nullptr, stream);
+}
+
+extern "C" int scone_opt_step_lean_ctl(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                                       uint64_t n, float *d_master, float *d_row_state, const scone_grad_ctl *d_ctl,
+                                       scone_stream_t stream) {
+  return opt_step_lean(h, "scone_opt_step_lean_ctl", cfg, d_row_ids, d_grad_rows, n, d_master, d_row_state, true, d_ctl, stream);
 }

@@ -31,6 +31,10 @@ static inline unsigned opt_begin(scone_handle *h, unsigned long long n) {
   return h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks ? (unsigned)h->opt_max_blocks : blocks;
 }
 
+// a wave-uniform float computed by the vector unit, put back where a kernel argument lives (a scalar register): the kernels read
+// gscale in every element's statement, and the _ctl entry points replace it by a product
+__device__ __forceinline__ float opt_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
+
 __device__ __forceinline__ uint32_t opt_i8_word(const float4 &x, float sf) {
   const float xs[4] = {x.x, x.y, x.z, x.w};
   uint32_t word = 0;

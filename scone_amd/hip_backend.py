@@ -384,6 +384,37 @@ def lean_rand16(seed: int, step: int, row_id: int, col: int) -> int:
     return int(L.lib().scone_lean_rand16(int(seed), int(step), int(row_id), int(col)))
 
 
+class GradCtl:
+    """``scone_grad_ctl``: the 24 device bytes :meth:`SconeTable.grad_ctl` fills and ``opt_step(..., ctl=)`` /
+    ``opt_step_lean(..., ctl=)`` read (include/scone_hip.h, "gradient norm, clipping and skipped steps").  ``coef`` (fp32) and
+    ``skip`` (int32: 0 or 1) are 0-dim views of the block on the device -- no synchronisation; ``coef`` is what the caller's dense
+    gradients are multiplied by (``torch._foreach_mul_(dense_grads, ctl.coef)``).  :meth:`read` synchronises."""
+
+    _DTYPE = np.dtype([("sqnorm", "<f8"), ("norm", "<f4"), ("coef", "<f4"), ("skip", "<u4"), ("reserved", "<u4")])
+
+    def __init__(self, device: torch.device) -> None:
+        self.buf = torch.empty(3, dtype=torch.float64, device=device)      # 24 bytes, 8-byte aligned; scone_grad_ctl_set writes all
+
+    def _field(self, name: str, dtype: torch.dtype) -> torch.Tensor:
+        at = getattr(L.SconeGradCtl, name).offset
+        return self.buf.view(torch.uint8)[at:at + 4].view(dtype)[0]
+
+    @property
+    def coef(self) -> torch.Tensor:
+        return self._field("coef", torch.float32)
+
+    @property
+    def skip(self) -> torch.Tensor:
+        return self._field("skip", torch.int32)
+
+    def read(self) -> dict:
+        """The five fields on the host (``sqnorm`` float64, ``norm`` / ``coef`` float32, ``skip`` / ``reserved`` int).
+        Synchronises."""
+        rec = self.buf.cpu().numpy().view(self._DTYPE)[0]
+        return {"sqnorm": np.float64(rec["sqnorm"]), "norm": np.float32(rec["norm"]), "coef": np.float32(rec["coef"]),
+                "skip": int(rec["skip"]), "reserved": int(rec["reserved"])}
+
+
 class BackwardPlan:
     """``scone_bwd_plan``: the sorted reference stream of one batch on one :class:`SconeTable` (include/scone_hip.h,
     "backward").  ``n_rows`` distinct rows have at least one of the ``n_refs`` references.  :meth:`rows` may be called any
@@ -1035,15 +1066,72 @@ class SconeTable:
                                              C.byref(n_refs), stream)
         return self._make_plan(rc, "scone_backward_plan_csr", plan, ntok, n_rows, n_refs)
 
+    def grad_sqnorm(self, grad_rows: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``scone_grad_sqnorm``: the squared norm of ``grad_rows`` (fp32 ``[U, d]``, what :meth:`BackwardPlan.rows` returns),
+        summed in double in the fixed order of include/scone_hip.h, "gradient norm, clipping and skipped steps".  Returns
+        ``(sq, row_sq)``: a 0-dim float64 device tensor and the per-row squared norms, a float64 ``[U]`` view of the call's
+        scratch.  ``scratch``: a contiguous float64 device tensor of at least ``_lib.grad_sqnorm_scratch(U)`` elements to use
+        instead of a fresh one (the tile sums follow the row sums in it).  At most three launches on the current stream; no
+        synchronisation."""
+        if grad_rows.dim() != 2 or grad_rows.shape[1] != self.dim or grad_rows.dtype != torch.float32:
+            raise ValueError(f"grad_sqnorm: grad_rows must be fp32 [U, {self.dim}], got {grad_rows.dtype} {tuple(grad_rows.shape)}")
+        grad_rows = grad_rows.to(device=self.device).contiguous()
+        n = grad_rows.shape[0]
+        need = L.grad_sqnorm_scratch(n)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.float64, device=self.device)
+        elif not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.numel() >= need
+                  and scratch.device == self.device and scratch.is_contiguous()):
+            raise ValueError(f"grad_sqnorm: scratch must be a contiguous float64 tensor of at least {need} elements on {self.device}")
+        sq = torch.empty((), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_grad_sqnorm(self._h, _ptr(grad_rows) if n else None, n, _ptr(scratch) if need else None, _ptr(sq),
+                                           stream.cuda_stream)
+        self._check(rc, "scone_grad_sqnorm")
+        if n:
+            grad_rows.record_stream(stream)                        # it may be a temporary of the caller
+        return sq, scratch[:n]
+
+    def grad_ctl(self, terms, grad_scale: float = 1.0, max_norm: Optional[float] = None, skip_nonfinite: bool = False) -> GradCtl:
+        """``scone_grad_ctl_set``: a :class:`GradCtl` from squared-norm ``terms`` that stay on the device -- a sequence of 0-dim
+        tensors (``grad_sqnorm``'s ``sq``, the dense parameters' squared norm, other shards') and floats, or one 1-D tensor; they
+        are added in the order given, in double.  ``grad_scale`` is the un-scaling factor the step will use (the norm is that of
+        the un-scaled gradient); ``max_norm=None`` does not clip; ``skip_nonfinite`` sets the block's ``skip`` when the sum is inf
+        or NaN.  One launch on the current stream; no synchronisation."""
+        if not isinstance(terms, torch.Tensor):
+            terms = list(terms)
+        if isinstance(terms, torch.Tensor):
+            vec = terms.reshape(-1).to(device=self.device, dtype=torch.float64)
+        elif len(terms) == 1 and isinstance(terms[0], torch.Tensor) and terms[0].dtype == torch.float64 and terms[0].device == self.device:
+            vec = terms[0].detach().reshape(1)                     # the usual case, the table's norm alone: no copy
+        elif terms:
+            vec = torch.stack([t.detach().to(device=self.device, dtype=torch.float64).reshape(()) if isinstance(t, torch.Tensor)
+                               else torch.tensor(float(t), dtype=torch.float64, device=self.device) for t in terms])
+        else:
+            vec = torch.zeros(0, dtype=torch.float64, device=self.device)
+        vec = vec.contiguous()
+        ctl = GradCtl(self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_grad_ctl_set(self._h, _ptr(vec) if vec.numel() else None, vec.numel(), float(grad_scale),
+                                            float("inf") if max_norm is None else float(max_norm), int(bool(skip_nonfinite)),
+                                            _ptr(ctl.buf), stream.cuda_stream)
+        self._check(rc, "scone_grad_ctl_set")
+        if vec.numel():
+            vec.record_stream(stream)
+        return ctl
+
     def opt_step(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, master: torch.Tensor, *, kind, lr: float, step: int = 1,
                  state1: Optional[torch.Tensor] = None, state2: Optional[torch.Tensor] = None, betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0) -> None:
+                 eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, ctl: Optional["GradCtl"] = None) -> None:
         """``scone_opt_step``: the fused sparse optimizer step (include/scone_hip.h, "optimizer step").  ``row_ids`` ``[U]``
         int64 ascending and distinct and ``grad_rows`` ``[U, d]`` fp32 are what :meth:`BackwardPlan.rows` returns.  ``master``,
         ``state1`` (Adam's m) and ``state2`` (Adam's v / Adagrad's sum of squares) are fp32 ``[row_end - row_begin, d]``,
         contiguous, on the table's device: the rows this handle owns, updated in place; the served table receives the updated
         rows in its own format.  ``kind``: ``"sgd"``, ``"adagrad"`` or ``"adam"``.  One kernel launch on the current stream; no
-        synchronisation."""
+        synchronisation.  ``ctl`` (a :class:`GradCtl`): ``scone_opt_step_ctl`` -- the kernel multiplies ``grad_scale`` by the block's
+        ``coef`` and changes nothing at all when its ``skip`` is set."""
         cfg = _opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step)
         owned = self.row_end - self.row_begin
         for name, t, needed in (("master", master, True), ("state1", state1, cfg.kind == L.OPT_ADAM),
@@ -1065,22 +1153,28 @@ class SconeTable:
         grad_rows = grad_rows.to(device=self.device).contiguous()
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            rc = L.lib().scone_opt_step(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
-                                        _ptr(state1), _ptr(state2), stream.cuda_stream)
-        self._check(rc, "scone_opt_step")
+            if ctl is None:
+                rc = L.lib().scone_opt_step(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
+                                            _ptr(state1), _ptr(state2), stream.cuda_stream)
+            else:
+                rc = L.lib().scone_opt_step_ctl(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(),
+                                                _ptr(master), _ptr(state1), _ptr(state2), _ptr(ctl.buf), stream.cuda_stream)
+        self._check(rc, "scone_opt_step" if ctl is None else "scone_opt_step_ctl")
         if row_ids.numel():                                        # they may be temporaries of the caller
             row_ids.record_stream(stream)
             grad_rows.record_stream(stream)
 
     def opt_step_lean(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, *, kind, lr: float, master: Optional[torch.Tensor] = None,
                       row_state: Optional[torch.Tensor] = None, eps: float = 1e-10, weight_decay: float = 0.0,
-                      grad_scale: float = 1.0, rounding="nearest", seed: int = 0, step: int = 1) -> None:
+                      grad_scale: float = 1.0, rounding="nearest", seed: int = 0, step: int = 1,
+                      ctl: Optional["GradCtl"] = None) -> None:
         """``scone_opt_step_lean``: the lean optimizer step (include/scone_hip.h, "lean optimizer step").  ``kind``: ``"sgd"`` or
         ``"rowwise_adagrad"`` (ONE fp32 accumulator per row: ``row_state``, fp32 ``[row_end - row_begin]``, contiguous, on the
         table's device, updated in place).  ``master`` given (fp32 ``[row_end - row_begin, d]``): it is updated in place and
         the served rows are re-stored in the table's format, as :meth:`opt_step` does.  ``master=None``: IN PLACE -- the served
         fp32 / bf16 rows are the weights; bf16 rows are rounded to ``"nearest"`` or ``"stochastic"`` (random bits keyed by
-        ``seed``, ``step``, the global row id and the column).  One kernel launch on the current stream; no synchronisation."""
+        ``seed``, ``step``, the global row id and the column).  One kernel launch on the current stream; no synchronisation.
+        ``ctl`` (a :class:`GradCtl`): ``scone_opt_step_lean_ctl``, as for :meth:`opt_step`."""
         cfg = _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step)
         owned = self.row_end - self.row_begin
         if master is None and self.fmt not in (L.FMT_F32, L.FMT_BF16):
@@ -1108,9 +1202,13 @@ class SconeTable:
         grad_rows = grad_rows.to(device=self.device).contiguous()
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            rc = L.lib().scone_opt_step_lean(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
-                                             _ptr(row_state), stream.cuda_stream)
-        self._check(rc, "scone_opt_step_lean")
+            if ctl is None:
+                rc = L.lib().scone_opt_step_lean(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
+                                                 _ptr(row_state), stream.cuda_stream)
+            else:
+                rc = L.lib().scone_opt_step_lean_ctl(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(),
+                                                     _ptr(master), _ptr(row_state), _ptr(ctl.buf), stream.cuda_stream)
+        self._check(rc, "scone_opt_step_lean" if ctl is None else "scone_opt_step_lean_ctl")
         if row_ids.numel():                                        # they may be temporaries of the caller
             row_ids.record_stream(stream)
             grad_rows.record_stream(stream)

@@ -220,6 +220,7 @@ class FGramOptimizer:
         self._set_fused(fused_backward)
         self.state1: Optional[torch.Tensor] = None     # Adam's m
         self.state2: Optional[torch.Tensor] = None     # Adam's v / Adagrad's sum of squares
+        self.last_ctl = None                           # the GradCtl of the last clipped / guarded step()
 
     def _set_fused(self, on: bool) -> None:
         on = bool(on)
@@ -262,55 +263,101 @@ class FGramOptimizer:
         if self.kind in ("adam", "adagrad") and self.state2 is None:
             self.state2 = torch.zeros_like(w.detach(), memory_format=torch.contiguous_format)
 
-    @torch.no_grad()
-    def step(self, grad_scale: float = 1.0) -> int:
-        """One update from ``module.weight.grad`` (``None``: nothing happens, ``t`` stays).  ``grad_scale`` multiplies the
-        gradient first (an un-scaling of a loss scale, a 1 / accumulation count).  Returns the number of rows updated."""
+    def _current_grad(self):
+        """``(row_ids, grad_rows)`` of the gradient on the module, or ``None``."""
         module = self.module
         if self.in_place:
-            return self._step_in_place(grad_scale)
+            return module.grad
         weight, grad = module.weight, module.weight.grad
         if grad is None:
-            return 0
+            return None
         if not grad.is_sparse:
             raise ValueError("FGramOptimizer.step: module.weight.grad must be the sparse gradient the lookup's backward sets")
         if not grad.is_coalesced():                      # set by the caller: its duplicates are added first, never by coalesce()
             none = torch.zeros(0, dtype=torch.int64, device=grad.device)
             grad = _add_coalesced(grad, none, torch.zeros((0, weight.shape[1]), dtype=grad.dtype, device=grad.device))
-        row_ids, grad_rows = grad._indices()[0], grad._values()
+        return grad._indices()[0], grad._values()
+
+    @torch.no_grad()
+    def grad_sqnorm(self) -> torch.Tensor:
+        """The squared norm of the gradient now on the module (both module kinds), as it is -- before any ``grad_scale`` -- a
+        0-dim float64 tensor on the table's device, summed in the fixed order of ``scone_grad_sqnorm``: the same bits on every
+        run.  No gradient: zero.  No synchronisation."""
+        table = self.module.cache.to_device()
+        grad = self._current_grad()
+        if grad is None:
+            return torch.zeros((), dtype=torch.float64, device=table.device)
+        return table.grad_sqnorm(grad[1])[0]
+
+    def found_nonfinite(self) -> bool:
+        """Whether the last ``step(...)`` that took a clipping / skipping argument found inf or NaN and skipped (with
+        ``skip_nonfinite=True``; without it nothing is ever skipped).  SYNCHRONISES: it reads ``last_ctl.skip``.  For the loss
+        scale's update and for skipping the caller's dense optimizers."""
+        return self.last_ctl is not None and bool(self.last_ctl.skip.item())
+
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0, *, max_norm: Optional[float] = None, extra_sqnorm=None,
+             skip_nonfinite: bool = False) -> int:
+        """One update from the gradient on the module (``None``: nothing happens, ``t`` stays).  ``grad_scale`` multiplies the
+        gradient first (an un-scaling of a loss scale, a 1 / accumulation count).  Returns the number of rows listed.
+
+        With ``max_norm``, ``extra_sqnorm`` or ``skip_nonfinite`` set, the step is clipped and guarded on the device, with no
+        host synchronise: ``grad_sqnorm()``, then ``table.grad_ctl([that, *extra_sqnorm], grad_scale, max_norm,
+        skip_nonfinite)`` -- kept as ``last_ctl`` -- then the ``_ctl`` step, whose kernel multiplies ``grad_scale`` by the block's
+        ``coef = min(1, max_norm / (norm + 1e-6))`` (``torch.nn.utils.clip_grad_norm_``'s) and writes nothing when the block's
+        ``skip`` is set.  ``extra_sqnorm``: the squared norm of the other gradients clipped together with the table's (the dense
+        parameters', other shards'), at the SAME loss scale -- a 0-dim device tensor, a float, or a sequence of them.
+        ``skip_nonfinite=True`` skips the step if any term is inf or NaN.  ``t`` ADVANCES ON A DEVICE-SKIPPED STEP TOO: the
+        host does not know the outcome.  A caller who wants Adam's ``t`` unchanged by a skipped step calls
+        :meth:`found_nonfinite` (a synchronise) and sets ``opt.t -= 1``.  With none of the three set, the step is the plain
+        one."""
+        ctl_road = max_norm is not None or extra_sqnorm is not None or bool(skip_nonfinite)
+        if self.fused_backward:
+            if ctl_road:
+                raise ValueError("FGramOptimizer.step: max_norm / extra_sqnorm / skip_nonfinite need the gradient's norm before the "
+                                 "first row is written, and fused_backward=True has updated the rows in the backward; use the "
+                                 "default road (fused_backward=False)")
+            n, self._fused_rows = self._fused_rows, 0    # the backwards have updated the rows already
+            return n
+        grad = self._current_grad()
+        if grad is None:
+            return 0
+        row_ids, grad_rows = grad
+        module = self.module
         table = module.cache.to_device()
         lo, hi = table.row_begin, table.row_end
+        ctl = None
+        if ctl_road:
+            if extra_sqnorm is None:
+                extra = []
+            elif isinstance(extra_sqnorm, (list, tuple)):
+                extra = list(extra_sqnorm)
+            else:
+                extra = [extra_sqnorm]
+            ctl = table.grad_ctl([table.grad_sqnorm(grad_rows)[0], *extra], grad_scale=grad_scale, max_norm=max_norm,
+                                 skip_nonfinite=skip_nonfinite)
+            self.last_ctl = ctl
         self.t += 1
         self._ensure_state()
 
         def own(x):                                      # the rows this handle owns: a contiguous view
             return None if x is None else x[lo:hi]
 
+        if self.in_place:
+            table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, row_state=own(self.state2), eps=self.eps,
+                                weight_decay=self.weight_decay, grad_scale=grad_scale, rounding=self.rounding, seed=self.seed,
+                                step=self.t, ctl=ctl)
+            return int(row_ids.numel())
+        weight = module.weight
         if self.kind == "rowwise_adagrad":
             table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, master=own(weight.detach()),
                                 row_state=own(self.state2), eps=self.eps, weight_decay=self.weight_decay, grad_scale=grad_scale,
-                                step=self.t)
+                                step=self.t, ctl=ctl)
         else:
             table.opt_step(row_ids, grad_rows, own(weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
                            state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
-                           grad_scale=grad_scale)
+                           grad_scale=grad_scale, ctl=ctl)
         module._touched = []                             # the served table is current: commit() has nothing to store
-        return int(row_ids.numel())
-
-    def _step_in_place(self, grad_scale: float) -> int:
-        module = self.module
-        if self.fused_backward:                          # the backwards have updated the rows already
-            n, self._fused_rows = self._fused_rows, 0
-            return n
-        if module.grad is None:
-            return 0
-        row_ids, grad_rows = module.grad
-        table = module.cache.to_device()
-        self.t += 1
-        self._ensure_state()
-        state = None if self.state2 is None else self.state2[table.row_begin:table.row_end]
-        table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, row_state=state, eps=self.eps,
-                            weight_decay=self.weight_decay, grad_scale=grad_scale, rounding=self.rounding, seed=self.seed, step=self.t)
         return int(row_ids.numel())
 
     def zero_grad(self, set_to_none: bool = True) -> None:
