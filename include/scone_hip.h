@@ -921,6 +921,71 @@ int scone_opt_step_ctl(scone_handle *h, const scone_opt_cfg *cfg, const int64_t 
 int scone_opt_step_lean_ctl(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                             uint64_t n, float *d_master, float *d_row_state, const scone_grad_ctl *d_ctl, scone_stream_t stream);
 
+/* ---- gradient accumulation: the sum of two sparse row gradients over micro-batches, kept on the device (new here; torch's
+ * coalesce() is the stock way, a sort with a host read of the output size).  Appended: SCONE_ABI_VERSION is unchanged and every
+ * entry point above keeps its bits and its behaviour.  A sparse row gradient is what scone_backward_rows returns: n int64 row
+ * ids, ascending and distinct, and fp32 rows [n, d], d = cfg.dim.  Two parts: scone_grad_merge_map + scone_grad_merge_rows add
+ * two such gradients that exist; scone_backward_row_ids + scone_backward_rows_acc add the gradient of a plan to an old one
+ * without ever storing it.  0xFFFFFFFF in a src array means "absent".
+ *
+ * 1. scone_grad_merge_map.  d_ids_a [n_a] and d_ids_b [n_b] are the two id lists.  d_ids_out, d_src_a and d_src_b have room for
+ *   n_a + n_b entries, d_pos_a for n_a, d_pos_b for n_b; d_scratch holds scone_grad_merge_scratch(n_a, n_b) bytes (that call does
+ *   no device work; its result does not decrease when an argument grows); d_n_out is ONE uint64 on the device.
+ *     d_ids_out[0, n_out)  the ascending union of the two lists
+ *     d_src_a[i]           the index in a of output row i, or absent; d_src_b[i] the same for b
+ *     d_pos_a[k]           the output row of a's row k; d_pos_b[k] the same for b
+ *     *d_n_out             n_out
+ *   Entries [n_out, n_a + n_b) of d_src_a / d_src_b are absent; those of d_ids_out are not written.  Ids are compared as signed
+ *   int64 and are never an address: every id finds its place by a binary search in the other list.  h_n_out != NULL: the stream
+ *   is synchronised ONCE and n_out returned, as the backward plan returns U; h_n_out == NULL: no synchronisation.  The call
+ *   allocates nothing.  n_a == 0, n_b == 0 and both are valid (the arrays of an empty list may be NULL).
+ *   A list that is not ascending and distinct is outside the contract: SCONE_ST_BAD_ID is raised (every entry is compared with
+ *   its predecessor) and the output is unspecified but bounded -- every d_src entry is absent or an index inside its list,
+ *   every d_pos entry is < n_a + n_b, n_out <= n_a + n_b, and nothing is written outside the capacities stated above.
+ *   SCONE_EINVAL, before any device work (scone_last_error names the reason, prefixed "scone_grad_merge_map: "):
+ *   n_a + n_b >= 2^32 - 1, a null pointer (d_scratch and d_n_out always; the others when their list is not empty), a handle
+ *   with dim == 0.
+ *
+ * 2. scone_grad_merge_rows.  d_src_a / d_src_b [n_out] are the map's; d_rows_a / d_rows_b the two gradients' rows, d_rows_out
+ *   fp32 [n_out, d], d % 4 == 0.  Output row i:
+ *     in a only   that row of a, bit for bit (-0.0 stays -0.0: a copy, not an add to zero)
+ *     in b only   that row of b, bit for bit
+ *     in both     a + b per element: ONE IEEE fp32 add, a the first operand, subnormals kept
+ *   (a row neither has -- possible only with a map of lists outside the contract -- is stored as +0.0).  Stream-ordered, ONE
+ *   launch, a wavefront per output row, its grid capped as scone_opt_step's (SCONE_OPT_MAX_BLOCKS applies); no allocation, no
+ *   atomics, plain vector stores.  n_out == 0: a no-op.  The output must not overlap an input.
+ *   SCONE_EINVAL (prefixed "scone_grad_merge_rows: "): d_rows_out equal to d_rows_a or d_rows_b, a null d_src_a / d_src_b /
+ *   d_rows_out with n_out > 0, n_out >= 2^32 - 1, a handle with dim == 0 or dim % 4 != 0.
+ *
+ * 3. scone_backward_row_ids: the U row ids of a plan, ascending, what scone_backward_rows writes to d_row_ids_out, without
+ *   computing a row.  One launch; U == 0: a no-op.  SCONE_ERANGE: rows_cap < U.  SCONE_EINVAL: a null plan / pointer, a plan of
+ *   another handle.
+ *
+ * 4. scone_backward_rows_acc.  d_src_old, d_src_new and d_pos_new are d_src_a, d_src_b and d_pos_b of
+ *   scone_grad_merge_map(a = the old gradient's ids, b = scone_backward_row_ids of the plan), n_out its count; d_rows_old the
+ *   old gradient's rows.  After the call d_rows_out [n_out, d] holds exactly the bits that
+ *     scone_backward_rows(h, plan, d_grad_out, grad_dtype, reduce, ids, rows, U), then
+ *     scone_grad_merge_rows(h, d_src_old, d_src_new, n_out, d_rows_old, rows, d_rows_out)
+ *   leave, and the fp32 [U, d] array `rows` never exists.  A row of one chunk is summed as stated under "backward", then
+ *   old + sum is stored (the sum itself where the old gradient has no such row); a row of several chunks goes through the
+ *   plan's partial slots, which are added in chunk order, and old is added last; a row only the old gradient has is copied.
+ *   Stream-ordered, at most three launches (SCONE_OPT_MAX_BLOCKS caps their grids), no allocation, no synchronisation, no
+ *   atomics.  U == 0: d_rows_out is a copy of d_rows_old.  n_out == 0: a no-op.  The plan's partials are scratch of the call, as
+ *   with scone_backward_rows.  d_pos_new is trusted to be the map's: an entry >= n_out is skipped, never an address.
+ *   SCONE_EINVAL (prefixed "scone_backward_rows_acc: "): what scone_backward_rows refuses (a null plan / pointer, a plan of
+ *   another handle, a bad grad_dtype / reduce, d % 8 != 0), d_rows_out equal to d_rows_old, n_out >= 2^32 - 1.  SCONE_ERANGE:
+ *   n_out < U. */
+int scone_grad_merge_scratch(uint64_t n_a, uint64_t n_b, uint64_t *bytes);
+int scone_grad_merge_map(scone_handle *h, const int64_t *d_ids_a, uint64_t n_a, const int64_t *d_ids_b, uint64_t n_b,
+                         int64_t *d_ids_out, uint32_t *d_src_a, uint32_t *d_src_b, uint32_t *d_pos_a, uint32_t *d_pos_b,
+                         void *d_scratch, uint64_t *d_n_out, uint64_t *h_n_out, scone_stream_t stream);
+int scone_grad_merge_rows(scone_handle *h, const uint32_t *d_src_a, const uint32_t *d_src_b, uint64_t n_out,
+                          const float *d_rows_a, const float *d_rows_b, float *d_rows_out, scone_stream_t stream);
+int scone_backward_row_ids(scone_handle *h, scone_bwd_plan *plan, int64_t *d_row_ids_out, uint64_t rows_cap, scone_stream_t stream);
+int scone_backward_rows_acc(scone_handle *h, scone_bwd_plan *plan, const void *d_grad_out, int32_t grad_dtype, int32_t reduce,
+                            const uint32_t *d_src_old, const uint32_t *d_src_new, const uint32_t *d_pos_new, uint64_t n_out,
+                            const float *d_rows_old, float *d_rows_out, scone_stream_t stream);
+
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of
  * every sequence in a decoding step, the last k tokens in a speculative-verify step, the new chunk of a chunked prefill.

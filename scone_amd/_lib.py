@@ -112,6 +112,14 @@ def grad_sqnorm_scratch(n: int) -> int:
     return int(out.value)
 
 
+def grad_merge_scratch(n_a: int, n_b: int) -> int:
+    """``scone_grad_merge_scratch``: the bytes ``scone_grad_merge_map`` needs as scratch.  Runs without a GPU."""
+    out = _U64(0)
+    if lib().scone_grad_merge_scratch(int(n_a), int(n_b), C.byref(out)) != OK:
+        raise ValueError("scone_grad_merge_scratch refused its arguments")
+    return int(out.value)
+
+
 # name -> (restype, argtypes); must list every symbol include/scone_hip.h declares
 SIGNATURES = {
     "scone_abi_version": (C.c_int, []),
@@ -219,6 +227,11 @@ SIGNATURES = {
     "scone_grad_ctl_set": (C.c_int, [_P, _P, _I32, C.c_double, C.c_double, _I32, _P, _P]),
     "scone_opt_step_ctl": (C.c_int, [_P, C.POINTER(OptCfg), _P, _P, _U64, _P, _P, _P, _P, _P]),
     "scone_opt_step_lean_ctl": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _U64, _P, _P, _P, _P]),
+    "scone_grad_merge_scratch": (C.c_int, [_U64, _U64, C.POINTER(_U64)]),
+    "scone_grad_merge_map": (C.c_int, [_P, _P, _U64, _P, _U64, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_U64), _P]),
+    "scone_grad_merge_rows": (C.c_int, [_P, _P, _P, _U64, _P, _P, _P, _P]),
+    "scone_backward_row_ids": (C.c_int, [_P, _P, _P, _U64, _P]),
+    "scone_backward_rows_acc": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _U64, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

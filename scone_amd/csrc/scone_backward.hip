@@ -652,6 +652,21 @@ extern "C" int scone_backward_rows(scone_handle *h, scone_bwd_plan *plan, const 
   return SCONE_OK;
 }
 
+extern "C" int scone_backward_row_ids(scone_handle *h, scone_bwd_plan *plan, int64_t *d_row_ids_out, uint64_t rows_cap,
+                                      scone_stream_t stream) {
+  if (!h) return SCONE_EINVAL;
+  if (!plan) return scone_fail(h, SCONE_EINVAL, "scone_backward_row_ids: null plan");
+  if (plan->h != h) return scone_fail(h, SCONE_EINVAL, "scone_backward_row_ids: the plan belongs to another handle");
+  const uint32_t U = plan->m.n_segs;
+  if (rows_cap < U) return scone_fail(h, SCONE_ERANGE, "scone_backward_row_ids: rows_cap below the plan's n_rows");
+  if (U == 0) return SCONE_OK;
+  if (!d_row_ids_out) return scone_fail(h, SCONE_EINVAL, "scone_backward_row_ids: null pointer");
+  SCONE_ON_DEVICE(h);
+  hipLaunchKernelGGL(k_bwd_row_ids, dim3(blocks_for(U)), dim3(BWD_THREADS), 0, (hipStream_t)stream, plan->d_row_id, U, d_row_ids_out);
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}
+
 extern "C" int scone_backward_counts(scone_handle *h, scone_bwd_plan *plan, int32_t *d_k_out, scone_stream_t stream) {
   if (!h) return SCONE_EINVAL;
   if (!plan) return scone_fail(h, SCONE_EINVAL, "scone_backward_counts: null plan");

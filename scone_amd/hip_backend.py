@@ -415,6 +415,21 @@ class GradCtl:
                 "skip": int(rec["skip"]), "reserved": int(rec["reserved"])}
 
 
+class GradMergeMap:
+    """What ``scone_grad_merge_map`` returns for two id lists ``a`` and ``b`` (include/scone_hip.h, "gradient accumulation"):
+    ``ids`` int64 ``[n_out]``, the ascending union; ``src_a`` / ``src_b`` int32 ``[n_out]``, the index in ``a`` / ``b`` of
+    every output row, ``-1`` (the library's ``0xFFFFFFFF``) where the list does not have it; ``pos_a`` ``[n_a]`` / ``pos_b``
+    ``[n_b]``, the output row of every input row; ``d_n_out``, the count on the device; ``n_out``, the count on the host
+    (``None`` from an unsynchronised call, whose arrays keep their capacity ``n_a + n_b``).  Made by
+    :meth:`SconeTable.grad_merge_map`."""
+
+    __slots__ = ("ids", "src_a", "src_b", "pos_a", "pos_b", "d_n_out", "n_out")
+
+    def __init__(self, ids, src_a, src_b, pos_a, pos_b, d_n_out, n_out) -> None:
+        self.ids, self.src_a, self.src_b, self.pos_a, self.pos_b = ids, src_a, src_b, pos_a, pos_b
+        self.d_n_out, self.n_out = d_n_out, n_out
+
+
 class BackwardPlan:
     """``scone_bwd_plan``: the sorted reference stream of one batch on one :class:`SconeTable` (include/scone_hip.h,
     "backward").  ``n_rows`` distinct rows have at least one of the ``n_refs`` references.  :meth:`rows` may be called any
@@ -425,6 +440,7 @@ class BackwardPlan:
     def __init__(self, table: "SconeTable", plan, ntok: int, n_rows: int, n_refs: int) -> None:
         self._table, self._p = table, plan
         self.ntok, self.n_rows, self.n_refs = int(ntok), int(n_rows), int(n_refs)
+        self._row_ids = None                      # row_ids(), once asked for: a plan does not change
 
     def close(self) -> None:
         if self._p is not None:
@@ -450,12 +466,48 @@ class BackwardPlan:
             raise SconeError("BackwardPlan: its table is closed")
         return self._p
 
+    def row_ids(self) -> torch.Tensor:
+        """``scone_backward_row_ids``: the plan's ``U`` row ids, int64 ascending -- :meth:`rows`'s first result without
+        computing a row.  Computed once and kept: treat the tensor as read-only."""
+        plan, t = self._plan(), self._table
+        if self._row_ids is None:
+            ids = torch.empty(self.n_rows, dtype=torch.int64, device=t.device)
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            t._check(L.lib().scone_backward_row_ids(t._h, plan, _ptr(ids) if self.n_rows else None, self.n_rows, stream),
+                     "scone_backward_row_ids")
+            self._row_ids = ids
+        return self._row_ids
+
+    def _rows_accumulate(self, grad_out: torch.Tensor, reduce: str, old) -> Tuple[torch.Tensor, torch.Tensor]:
+        plan, t = self._plan(), self._table
+        old_ids, old_rows = t._sparse_operand("rows(accumulate=)", *old)
+        m = t.grad_merge_map(old_ids, self.row_ids())
+        out = torch.empty((m.n_out, t.dim), dtype=torch.float32, device=t.device)
+        with torch.cuda.device(t.device):
+            stream = torch.cuda.current_stream(t.device)
+            rc = L.lib().scone_backward_rows_acc(t._h, plan, _ptr(grad_out) if self.n_rows else None, _DT[grad_out.dtype],
+                                                 _REDUCE[reduce], _ptr(m.src_a), _ptr(m.src_b), _ptr(m.pos_b), m.n_out,
+                                                 _ptr(old_rows) if old_rows.shape[0] else None, _ptr(out) if m.n_out else None,
+                                                 stream.cuda_stream)
+        t._check(rc, "scone_backward_rows_acc")
+        for x in (grad_out, old_rows, m.src_a, m.src_b, m.pos_b):
+            if x.numel():
+                x.record_stream(stream)
+        return m.ids, out
+
     def rows(self, grad_out: torch.Tensor, reduce: str = "mean",
-             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, *,
+             accumulate: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``scone_backward_rows``: ``(row_ids [U] int64 ascending, grad_rows [U, d] fp32)``, the payload of a coalesced
         ``torch.sparse_coo_tensor``.  ``grad_out``: ``[ntok, d]`` (or ``[B, T, d]``) fp32 / fp16 / bf16 on the table's device.
         ``out = (row_ids, grad_rows)``: the caller's buffers of at least ``n_rows`` rows; views of their first ``U`` rows
-        are returned."""
+        are returned.
+
+        ``accumulate = (old_ids, old_rows)``, a sparse row gradient that is already there (int64 ascending and distinct, fp32
+        ``[n, d]``, on the table's device): ``scone_backward_rows_acc`` (include/scone_hip.h, "gradient accumulation").  The
+        merged ``(ids, rows)`` is returned -- the bits of :meth:`rows` followed by :meth:`SconeTable.grad_merge` ``(old, new)``
+        -- and the fp32 ``[U, d]`` gradient of this plan is never stored.  One 8-byte synchronise for the size of the union;
+        ``out`` is not taken on this road."""
         plan, t = self._plan(), self._table
         if grad_out.dtype not in _DT:
             raise ValueError(f"grad_out must be fp32, fp16 or bf16, not {grad_out.dtype}")
@@ -463,6 +515,12 @@ class BackwardPlan:
             raise ValueError(f"grad_out must hold [{self.ntok}, {t.dim}] elements, got {tuple(grad_out.shape)}")
         if not (grad_out.is_cuda and grad_out.device == t.device and grad_out.is_contiguous()):
             grad_out = grad_out.to(device=t.device).contiguous()
+        if accumulate is not None:
+            if out is not None:
+                raise ValueError("rows: out= and accumulate= do not go together (the size of the union is not known beforehand)")
+            if reduce not in _REDUCE:
+                raise ValueError(f"unknown reduce {reduce!r}")
+            return self._rows_accumulate(grad_out, reduce, accumulate)
         if out is None:
             ids = torch.empty(self.n_rows, dtype=torch.int64, device=t.device)
             rows = torch.empty((self.n_rows, t.dim), dtype=torch.float32, device=t.device)
@@ -1065,6 +1123,86 @@ class SconeTable:
                                              ids.data_ptr() if ids.numel() else None, ntok, C.byref(plan), C.byref(n_rows),
                                              C.byref(n_refs), stream)
         return self._make_plan(rc, "scone_backward_plan_csr", plan, ntok, n_rows, n_refs)
+
+    def _sparse_operand(self, who: str, ids: torch.Tensor, rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(ids, rows)`` of a sparse row gradient, checked and made contiguous on the table's device."""
+        if ids.dim() != 1 or ids.dtype != torch.int64:
+            raise ValueError(f"{who}: row ids must be int64 [n], got {ids.dtype} {tuple(ids.shape)}")
+        if rows.dim() != 2 or rows.shape != (ids.shape[0], self.dim) or rows.dtype != torch.float32:
+            raise ValueError(f"{who}: rows must be fp32 [{ids.shape[0]}, {self.dim}], got {rows.dtype} {tuple(rows.shape)}")
+        return ids.to(device=self.device).contiguous(), rows.to(device=self.device).contiguous()
+
+    def grad_merge_map(self, ids_a: torch.Tensor, ids_b: torch.Tensor, sync: bool = True) -> GradMergeMap:
+        """``scone_grad_merge_map``: the union of two ascending lists of distinct int64 row ids and the maps between the three
+        row numberings (include/scone_hip.h, "gradient accumulation"), a :class:`GradMergeMap`.  ``sync=True`` synchronises
+        the current stream once (8 bytes) and trims the results to ``n_out``; ``sync=False`` does not synchronise and leaves
+        them at their capacity ``n_a + n_b`` with ``n_out = None`` (the count is the device tensor ``d_n_out``)."""
+        for x in (ids_a, ids_b):
+            if x.dim() != 1 or x.dtype != torch.int64:
+                raise ValueError(f"grad_merge_map: row ids must be int64 [n], got {x.dtype} {tuple(x.shape)}")
+        ids_a, ids_b = ids_a.to(device=self.device).contiguous(), ids_b.to(device=self.device).contiguous()
+        n_a, n_b = ids_a.numel(), ids_b.numel()
+        dev = self.device
+        ids = torch.empty(n_a + n_b, dtype=torch.int64, device=dev)
+        words = torch.empty(3 * (n_a + n_b) + 2, dtype=torch.int32, device=dev)       # src_a | src_b | pos_a | pos_b | n_out
+        src_a, src_b = words[:n_a + n_b], words[n_a + n_b:2 * (n_a + n_b)]
+        pos_a, pos_b = words[2 * (n_a + n_b):2 * (n_a + n_b) + n_a], words[2 * (n_a + n_b) + n_a:3 * (n_a + n_b)]
+        d_n_out = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.grad_merge_scratch(n_a, n_b), dtype=torch.uint8, device=dev)
+        h_n_out = C.c_uint64(0)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            rc = L.lib().scone_grad_merge_map(self._h, _ptr(ids_a) if n_a else None, n_a, _ptr(ids_b) if n_b else None, n_b,
+                                              _ptr(ids), _ptr(src_a), _ptr(src_b), _ptr(pos_a), _ptr(pos_b), _ptr(scratch),
+                                              _ptr(d_n_out), C.byref(h_n_out) if sync else None, stream.cuda_stream)
+        self._check(rc, "scone_grad_merge_map")
+        for x in (ids_a, ids_b, scratch):
+            if x.numel():
+                x.record_stream(stream)
+        if not sync:
+            return GradMergeMap(ids, src_a, src_b, pos_a, pos_b, d_n_out, None)
+        n = int(h_n_out.value)
+        return GradMergeMap(ids[:n], src_a[:n], src_b[:n], pos_a, pos_b, d_n_out, n)
+
+    def grad_merge_rows(self, m: GradMergeMap, rows_a: torch.Tensor, rows_b: torch.Tensor,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_grad_merge_rows``: the rows of the merged gradient, fp32 ``[n_out, d]`` -- a row one operand has is that row,
+        bit for bit; a row both have is ``a + b``, one fp32 add.  ``m``: a synchronised :class:`GradMergeMap` of the two id
+        lists.  One launch on the current stream."""
+        if m.n_out is None:
+            raise ValueError("grad_merge_rows: the map must know n_out (grad_merge_map(sync=True))")
+        for x in (rows_a, rows_b):
+            if x.dim() != 2 or x.shape[1] != self.dim or x.dtype != torch.float32 or not (x.is_cuda and x.device == self.device
+                                                                                          and x.is_contiguous()):
+                raise ValueError(f"grad_merge_rows: rows must be contiguous fp32 [n, {self.dim}] on {self.device}")
+        if rows_a.shape[0] != m.pos_a.numel() or rows_b.shape[0] != m.pos_b.numel():
+            raise ValueError("grad_merge_rows: the rows are not those of the map's lists")
+        if out is None:
+            out = torch.empty((m.n_out, self.dim), dtype=torch.float32, device=self.device)
+        elif not (out.dtype == torch.float32 and out.dim() == 2 and out.shape[1] == self.dim and out.shape[0] >= m.n_out
+                  and out.device == self.device and out.is_contiguous()):
+            raise ValueError(f"grad_merge_rows: out must be a contiguous fp32 [>= {m.n_out}, {self.dim}] tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_grad_merge_rows(self._h, _ptr(m.src_a), _ptr(m.src_b), m.n_out,
+                                               _ptr(rows_a) if rows_a.shape[0] else None,
+                                               _ptr(rows_b) if rows_b.shape[0] else None, _ptr(out) if out.shape[0] else None,
+                                               stream.cuda_stream)
+        self._check(rc, "scone_grad_merge_rows")
+        for x in (rows_a, rows_b, m.src_a, m.src_b):
+            if x.numel():
+                x.record_stream(stream)
+        return out[:m.n_out]
+
+    def grad_merge(self, ids_a: torch.Tensor, rows_a: torch.Tensor, ids_b: torch.Tensor,
+                   rows_b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The sum of two sparse row gradients ``(ids, rows)`` -- int64 ascending and distinct, fp32 ``[n, d]``, what
+        :meth:`BackwardPlan.rows` returns -- as one more: ``scone_grad_merge_map`` (one 8-byte synchronise for the size of the
+        union), then ``scone_grad_merge_rows``.  Gradient accumulation over micro-batches without ``coalesce()``."""
+        ids_a, rows_a = self._sparse_operand("grad_merge", ids_a, rows_a)
+        ids_b, rows_b = self._sparse_operand("grad_merge", ids_b, rows_b)
+        m = self.grad_merge_map(ids_a, ids_b)
+        return m.ids, self.grad_merge_rows(m, rows_a, rows_b)
 
     def grad_sqnorm(self, grad_rows: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``scone_grad_sqnorm``: the squared norm of ``grad_rows`` (fp32 ``[U, d]``, what :meth:`BackwardPlan.rows` returns),

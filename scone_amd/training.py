@@ -44,6 +44,23 @@ def _add_coalesced(old: torch.Tensor, row_ids: torch.Tensor, grad_rows: torch.Te
     return torch.sparse_coo_tensor(ids[None], rows, tuple(old.shape), is_coalesced=True)
 
 
+def _is_library_rows(rows: torch.Tensor, table) -> bool:
+    """fp32 ``[n, d]`` rows on the table's device: what ``SconeTable.grad_merge`` takes."""
+    return (isinstance(rows, torch.Tensor) and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == table.dim
+            and rows.device == table.device and table.dim % 4 == 0)
+
+
+def _library_operand(grad: Optional[torch.Tensor], table):
+    """``(row_ids, grad_rows)`` of a sparse gradient the library adds to (include/scone_hip.h, "gradient accumulation"): a
+    coalesced ``[N, d]`` COO tensor with fp32 values on the table's device -- what the backward sets.  Anything else (none, or a
+    gradient set by the caller: not coalesced, another dtype or device) is ``None`` and stays with :func:`_add_coalesced`."""
+    if grad is None or not grad.is_sparse or grad.layout != torch.sparse_coo or not grad.is_coalesced():
+        return None
+    if grad.sparse_dim() != 1 or not _is_library_rows(grad._values(), table):
+        return None
+    return grad._indices()[0], grad._values()
+
+
 class _Lookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, base, module, input_ids, cu_seqlens, reduce, out_dtype):
@@ -74,9 +91,15 @@ class _Lookup(torch.autograd.Function):
             if ctx.needs_input_grad[0] and fused is not None:
                 fused._apply_backward(plan, grad_out, ctx.reduce)
             elif ctx.needs_input_grad[0]:
-                row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
-                # set on the module, not returned: autograd's accumulation re-creates a sparse gradient without its coalesced flag
-                module._accumulate(row_ids, grad_rows)
+                old = module._mergeable_grad()
+                if old is not None:
+                    # a gradient is already there: the library adds this batch's rows to it, and they are never stored
+                    module._set_merged(plan.row_ids(), *plan.rows(grad_out, ctx.reduce, accumulate=old))
+                else:
+                    row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
+                    # set on the module, not returned: autograd's accumulation re-creates a sparse gradient without its
+                    # coalesced flag
+                    module._accumulate(row_ids, grad_rows)
             if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
                 grad_base = grad_out
                 if module.cache.lookup_mode == "longest_suffix":     # a matched f-gram replaced the base row
@@ -95,7 +118,9 @@ class TrainableFGramTable(nn.Module):
     never reads a table row.  ``forward`` runs the existing one-launch lookup (``embed_tokens``, with ``base=`` when given;
     on a ``lookup_mode="longest_suffix"`` cache with ``base=`` the paper's form, ``cache.table.embed_base``), so its output
     has the serving path's bits exactly.  ``backward`` sets ``weight.grad`` itself, to a coalesced ``torch.sparse_coo_tensor``
-    (a backward onto a gradient that is already there adds to it and coalesces; ``torch.autograd.grad`` does not see it; use an
+    (a backward onto a gradient that is already there adds to it on the device -- ``scone_backward_rows_acc``, include/scone_hip.h
+    "gradient accumulation": the new rows are never stored; a gradient the caller has set that is not coalesced, fp32 and on the
+    table's device is added by torch glue instead; ``torch.autograd.grad`` does not see it; use an
     optimiser that takes sparse gradients: ``SGD``, ``SparseAdam``, ``Adagrad`` -- or :class:`FGramOptimizer`, which updates
     the served table in the same launch), and returns ``grad_base = grad_out``
     (cover mode) or ``grad_out * (K == 0)`` (longest suffix: a matched f-gram replaced the base row).
@@ -118,7 +143,20 @@ class TrainableFGramTable(nn.Module):
                 out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         return _Lookup.apply(self.weight, base, self, input_ids, cu_seqlens, reduce, out_dtype)
 
+    def _mergeable_grad(self):
+        """``(row_ids, grad_rows)`` of ``weight.grad`` if the library can add to it (``SconeTable.grad_merge``: coalesced, fp32,
+        on the table's device), else ``None`` -- no gradient, or one the caller has set that stays on ``_add_coalesced``."""
+        return _library_operand(self.weight.grad, self.cache.to_device())
+
+    def _set_merged(self, touched_ids: torch.Tensor, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        self._touched.append(touched_ids)
+        self.weight.grad = torch.sparse_coo_tensor(row_ids[None], grad_rows, tuple(self.weight.shape), is_coalesced=True)
+
     def _accumulate(self, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        old = self._mergeable_grad()
+        if old is not None and _is_library_rows(grad_rows, self.cache.to_device()):
+            self._set_merged(row_ids, *self.cache.to_device().grad_merge(*old, row_ids, grad_rows))
+            return
         self._touched.append(row_ids)
         sparse = torch.sparse_coo_tensor(row_ids[None], grad_rows, tuple(self.weight.shape), is_coalesced=True)
         weight = self.weight
@@ -160,7 +198,23 @@ class InPlaceFGramTable(nn.Module):
                 out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         return _Lookup.apply(self.anchor, base, self, input_ids, cu_seqlens, reduce, out_dtype)
 
+    def _mergeable_grad(self):
+        """``grad`` if the library can add to it (fp32 rows and int64 ids on the table's device), else ``None``."""
+        if self.grad is None:
+            return None
+        ids, rows = self.grad
+        table = self.cache.to_device()
+        ok = _is_library_rows(rows, table) and ids.dtype == torch.int64 and ids.dim() == 1 and ids.device == table.device
+        return (ids, rows) if ok and ids.numel() == rows.shape[0] else None
+
+    def _set_merged(self, touched_ids: torch.Tensor, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        self.grad = (row_ids, grad_rows)
+
     def _accumulate(self, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        old = self._mergeable_grad()
+        if old is not None and _is_library_rows(grad_rows, self.cache.to_device()):
+            self.grad = self.cache.to_device().grad_merge(*old, row_ids, grad_rows)
+            return
         if self.grad is not None:
             old = torch.sparse_coo_tensor(self.grad[0][None], self.grad[1], self.shape, is_coalesced=True)
             both = _add_coalesced(old, row_ids, grad_rows)
@@ -189,7 +243,8 @@ class FGramOptimizer:
     place").  The lookup's backward itself updates the served rows, so the fp32 ``[U, d]`` gradient is never stored:
     ``module.grad`` stays ``None``, ``t`` advances once per backward, and the update reads ``lr``, ``eps``, ``weight_decay`` and
     the attribute ``grad_scale`` at backward time.  TWO BACKWARDS ARE TWO UPDATES -- nothing is left to accumulate into -- so
-    gradient accumulation over micro-batches needs the default road.  ``step()`` only returns the number of rows updated since
+    gradient accumulation over micro-batches needs the default road (where a second backward adds to the gradient on the device:
+    include/scone_hip.h, "gradient accumulation").  ``step()`` only returns the number of rows updated since
     the last ``step()`` (its ``grad_scale`` argument is not used) and ``zero_grad()`` has nothing to do.  One backward of this
     road leaves the bits one backward + ``step(grad_scale)`` of the default road leaves."""
 
