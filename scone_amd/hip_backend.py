@@ -441,6 +441,7 @@ class BackwardPlan:
         self._table, self._p = table, plan
         self.ntok, self.n_rows, self.n_refs = int(ntok), int(n_rows), int(n_refs)
         self._row_ids = None                      # row_ids(), once asked for: a plan does not change
+        self._row_ids_stream, self._row_ids_ready = None, None    # where they were computed, and the event recorded behind that
 
     def close(self) -> None:
         if self._p is not None:
@@ -468,14 +469,23 @@ class BackwardPlan:
 
     def row_ids(self) -> torch.Tensor:
         """``scone_backward_row_ids``: the plan's ``U`` row ids, int64 ascending -- :meth:`rows`'s first result without
-        computing a row.  Computed once and kept: treat the tensor as read-only."""
+        computing a row.  Computed once, on the stream that is current then, and kept: treat the tensor as read-only.  A call
+        under another current stream -- `rows(accumulate=)` makes one -- has that stream wait for an event recorded behind the
+        launch (no host synchronisation; nothing on the stream that computed them)."""
         plan, t = self._plan(), self._table
+        stream = torch.cuda.current_stream(t.device)
         if self._row_ids is None:
             ids = torch.empty(self.n_rows, dtype=torch.int64, device=t.device)
-            stream = torch.cuda.current_stream(t.device).cuda_stream
-            t._check(L.lib().scone_backward_row_ids(t._h, plan, _ptr(ids) if self.n_rows else None, self.n_rows, stream),
+            t._check(L.lib().scone_backward_row_ids(t._h, plan, _ptr(ids) if self.n_rows else None, self.n_rows, stream.cuda_stream),
                      "scone_backward_row_ids")
             self._row_ids = ids
+            if self.n_rows:                       # a plan serves every stream: a later caller on another one waits for this
+                self._row_ids_stream = stream.cuda_stream
+                self._row_ids_ready = torch.cuda.Event()
+                self._row_ids_ready.record(stream)
+        elif self._row_ids_ready is not None and stream.cuda_stream != self._row_ids_stream:
+            stream.wait_event(self._row_ids_ready)                # nothing on the stream that made them
+            self._row_ids.record_stream(stream)
         return self._row_ids
 
     def _rows_accumulate(self, grad_out: torch.Tensor, reduce: str, old) -> Tuple[torch.Tensor, torch.Tensor]:
