@@ -145,7 +145,8 @@ const char *scone_last_error(const scone_handle *h);
  * or a position id -- the caller's or the default one -- outside [0, n_pos) of a given d_wpe, see "Ids out of range" at
  * scone_embed; also a scone_embed_select position outside the batch, bit 1: f-gram id outside the table, bit 2: index
  * full, bit 3: the cache of cold rows of a pinned-host lookup had no evictable slot for a row -- sized so that it cannot
- * happen; the affected tokens read a wrong row); synchronises the stream, returns the bits in *bits and clears them. */
+ * happen; the affected tokens read a wrong row, bit 4: scone_backward_rows_dn found more rows in its plan than rows_cap and
+ * wrote none, *d_n_out = 0); synchronises the stream, returns the bits in *bits and clears them. */
 int scone_status(scone_handle *h, uint32_t *bits, scone_stream_t stream);
 /* The cache of cold rows of a pinned-host table (cfg.stage_tokens > 0): its row slots, the rows copied host -> HBM since the
  * cache was created (every miss crosses PCIe once), the chunks prepared and the tokens per chunk actually used (smaller than
@@ -985,6 +986,108 @@ int scone_backward_row_ids(scone_handle *h, scone_bwd_plan *plan, int64_t *d_row
 int scone_backward_rows_acc(scone_handle *h, scone_bwd_plan *plan, const void *d_grad_out, int32_t grad_dtype, int32_t reduce,
                             const uint32_t *d_src_old, const uint32_t *d_src_new, const uint32_t *d_pos_new, uint64_t n_out,
                             const float *d_rows_old, float *d_rows_out, scone_stream_t stream);
+
+/* ---- backward and optimizer step without a host synchronisation: a step that can be captured (new here; appended,
+ * SCONE_ABI_VERSION unchanged; every entry point above keeps its bits, its refusals and its place in the stream contract).
+ * What it is for: scone_backward_plan reads its counts back (one synchronisation), allocates the partial slots from them and
+ * allocates and frees its scratch inside the call, so it is the one call of a training step that keeps the host in lockstep
+ * with the device and out of a hipGraph.  The forms below hold the same buffers in a CONTEXT that is allocated once, leave the
+ * counts on the device, and give the same bits: plan, rows, norm, control block and optimizer step can be enqueued without the
+ * host waiting, and captured once and replayed on new tokens.
+ *
+ * 1. Context.  scone_backward_ctx_create(h, max_tokens, &ctx) allocates everything a plan of up to max_tokens positions can
+ *   need on this handle, in one device allocation: the match records [max_tokens, ELL width] (the context's matcher uses no
+ *   stream workspace, so it never allocates either), the build's scratch arrays and rocPRIM's scratch, the plan arrays, and the
+ *   partial slots at their worst case.  With R = max_tokens * max_n (max_n + 1) / 2 references at most (R = max_tokens in
+ *   longest_suffix mode) and C = scone_backward_chunk(): a row of r > C references has ceil(r / C) <= (r - 1) / C + 1 chunks;
+ *   m such rows hold R' <= R references and m <= R' / (C + 1), so their chunks -- the partial slots -- number at most
+ *     (R' - m) / C + m  <=  R' / C + (R' / (C + 1)) (C - 1) / C  =  2 R' / (C + 1)  <=  floor(2 R / (C + 1)),
+ *   reached when every row has C + 1 references.  scone_backward_ctx_partial_slots(R, &slots) returns floor(2 R / (C + 1))
+ *   (no device work; R >= 2^32: SCONE_EINVAL); the context holds min(that, the chunk bound R / C + min(R, owned rows) + 1)
+ *   slots of d floats.  The bounds are checked against each other at creation, the counts of a plan against them by
+ *   scone_backward_ctx_counts on the host and by every kernel of scone_backward_rows_dn on the device.
+ *   scone_backward_ctx_bytes reports the device memory held; scone_backward_ctx_destroy frees it (NULL: a no-op; not while work
+ *   that uses the context is in flight).  A context is used by one host thread at a time and belongs to its handle.
+ *   SCONE_EINVAL (prefixed "scone_backward_ctx_create: "): what scone_backward_plan refuses of the handle (dim == 0, d % 8 != 0,
+ *   2^32 - 1 rows or more), max_tokens < 0, max_tokens > 2^31 - 1 or R >= 2^32, a null out.  Synchronises (it allocates).
+ *
+ * 2. Plans.  scone_backward_plan_dn (rectangle [B, T]) and scone_backward_plan_varlen_dn (packed, d_cu_seqlens [n_seqs + 1])
+ *   build in the context the plan that scone_backward_plan / scone_backward_plan_varlen return for the same batch: the same id
+ *   lists, the same stable sort, the same chunks and partial slots -- the same enqueue sequence, over the context's buffers.
+ *   No synchronisation, no allocation, no free; the counts (U, the references, the chunks) stay on the device inside the
+ *   context.  A new plan overwrites the previous one; stream order protects consumers that are already enqueued, so plans and
+ *   their consumers belong on one stream (or are ordered by the caller's events).  B * T == 0, n_seqs == 0 and a batch without a
+ *   hit are empty plans: every count is 0.  Capture: a plan whose batch can have more than 2^20 references (B * T * max_n
+ *   (max_n + 1) / 2; rocPRIM's merge-sort limit) is REFUSED while `stream` is capturing (SCONE_EINVAL, nothing enqueued): above
+ *   that size the sort runs kernels with a private segment, and replaying a graph that holds them faulted on the runtime this
+ *   was developed on.  Called eagerly such a plan is as sync-free as any other.  SCONE_ERANGE: more positions than max_tokens.  SCONE_EINVAL: a null ctx / pointer, a
+ *   context of another handle, negative sizes, and for the packed form what scone_backward_plan_varlen refuses.  There is NO
+ *   form for the caller's CSR lists: scone_backward_plan_csr needs the owned-reference count on the host before it can size
+ *   anything, which is the synchronisation this section removes.
+ *   scone_backward_ctx_counts(ctx, &n_rows, &n_refs, stream) is the synchronising read of U and the reference count of the
+ *   plan last enqueued on `stream` (either pointer may be NULL); SCONE_ESTATE if a count is outside the context's bounds.
+ *
+ * 3. Rows.  scone_backward_rows_dn(h, ctx, d_grad_out, grad_dtype, reduce, d_row_ids_out, d_grad_rows_out, rows_cap, d_n_out)
+ *   writes, with U read on the device,
+ *     d_row_ids_out[0, U)    bit for bit what scone_backward_rows writes for a plan of the same batch
+ *     d_grad_rows_out[0, U)  likewise bit for bit (the walk of a chunk and the order of the partials are the same code)
+ *     *d_n_out               U (ONE uint64 on the device)
+ *   Rows [U, rows_cap) of both arrays are not touched.  U > rows_cap: NOTHING is written to the two arrays, *d_n_out = 0 and the
+ *   sticky status bit 4 is raised (scone_status); every workgroup of every launch takes this exit before its first store, so
+ *   an optimizer step behind it that takes n from d_n_out changes nothing.  At most three launches; their grids are sized from
+ *   the host-known bounds of the plan, capped, and walk the device counts grid-stride.  No synchronisation, no allocation.
+ *   The partial slots are scratch of the call, as with scone_backward_rows.  SCONE_EINVAL: a null ctx / d_n_out, a context of
+ *   another handle, a bad grad_dtype / reduce, a null d_grad_out / output array unless the plan is empty on the host's
+ *   knowledge (no positions) or rows_cap == 0.
+ *
+ * 4. Optimizer steps.  scone_opt_step_dn and scone_opt_step_lean_dn are scone_opt_step / scone_opt_step_lean -- or, with
+ *   d_ctl != NULL, scone_opt_step_ctl / scone_opt_step_lean_ctl -- with n = min(*d_n, n_cap), read on the device by every
+ *   wavefront (a scalar load) before it touches a row; d_row_ids / d_grad_rows have room for n_cap rows.  The same kernels,
+ *   instantiated for a count on the device: every bit of master, state, table and scales equals the by-value call with that n.
+ *   ONE launch (grid sized from n_cap as the by-value call sizes it from n), no synchronisation, no allocation.  n_cap == 0: a
+ *   no-op.  The refusals of the by-value calls, plus a null d_n.
+ *
+ * 5. Squared norm.  scone_grad_sqnorm_dn(h, d_grad_rows, d_n, n_cap, d_scratch, d_sq_out): d_scratch holds
+ *   scone_grad_sqnorm_scratch(n_cap) doubles -- Q_r at [0, n_cap), the tile sums behind them.  With n = min(*d_n, n_cap),
+ *   *d_sq_out and Q_r, r < n, have the bits scone_grad_sqnorm(n) gives.  Proof: Q_r is computed per row by the same code.  The
+ *   call reduces the ceil(n_cap / 1024) tiles of the capacity, of which the first ceil(n / 1024) are those of
+ *   scone_grad_sqnorm(n): a thread's partial sum of a tile adds the rows r < n it owns in the same order, and a tile past n adds
+ *   nothing, so its tree yields +0.0.  In the total, thread t adds P_(t + 256 i) in ascending i: the tiles of the by-value call
+ *   first, then +0.0 terms.  Every sum here starts at +0.0 and holds only squares and sums of squares, so it is never -0.0, and
+ *   x + (+0.0) has the bits of x for every such x (NaN and +inf included).  The tree that follows is the same.  Three launches,
+ *   no synchronisation, no allocation.  Q_r, r >= n, is not written.  SCONE_EINVAL: as scone_grad_sqnorm, plus a null d_n.
+ *   scone_grad_ctl_set is unchanged: it never took a count.
+ *
+ * The stream.  Every call of this section that enqueues work takes `stream` last: a hipStream_t passed as void * (what
+ * scone_stream_t is; NULL = the default stream), the stream all of its device work is enqueued on.
+ *
+ * Scalars under capture.  The steps still take their hyper-parameters by value (scone_opt_scalars_of / scone_lean_scalars_of
+ * run on the host): Adam's step t inside alpha and the stochastic rounding's `step` are part of a captured launch and a
+ * replayed graph repeats them AS CAPTURED.  SGD, Adagrad, row-wise Adagrad and round-to-nearest have no such scalar.
+ *
+ * Left out, and meant to be: scone_backward_apply_lean in this form (the fused backward + lean step still takes a
+ * scone_bwd_plan), and accumulation (scone_backward_rows_acc, scone_grad_merge_*) in this form -- a step that accumulates over
+ * micro-batches takes the by-value road. */
+typedef struct scone_bwd_ctx scone_bwd_ctx;
+int scone_backward_ctx_partial_slots(uint64_t max_refs, uint64_t *slots);
+int scone_backward_ctx_create(scone_handle *h, int64_t max_tokens, scone_bwd_ctx **out);
+int scone_backward_ctx_bytes(scone_bwd_ctx *ctx, uint64_t *bytes);
+void scone_backward_ctx_destroy(scone_bwd_ctx *ctx);
+int scone_backward_plan_dn(scone_handle *h, scone_bwd_ctx *ctx, const int32_t *d_tok, int32_t B, int32_t T, void *stream);
+int scone_backward_plan_varlen_dn(scone_handle *h, scone_bwd_ctx *ctx, const int32_t *d_tok, const int32_t *d_cu_seqlens,
+                                  int32_t n_seqs, int64_t total_tokens, void *stream);
+int scone_backward_ctx_counts(scone_bwd_ctx *ctx, uint64_t *h_n_rows, uint64_t *h_n_refs, void *stream);
+int scone_backward_rows_dn(scone_handle *h, scone_bwd_ctx *ctx, const void *d_grad_out, int32_t grad_dtype, int32_t reduce,
+                           int64_t *d_row_ids_out, float *d_grad_rows_out, uint64_t rows_cap, uint64_t *d_n_out,
+                           void *stream);
+int scone_opt_step_dn(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                      const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_state1, float *d_state2,
+                      const scone_grad_ctl *d_ctl, void *stream);
+int scone_opt_step_lean_dn(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                           const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_row_state, const scone_grad_ctl *d_ctl,
+                           void *stream);
+int scone_grad_sqnorm_dn(scone_handle *h, const float *d_grad_rows, const uint64_t *d_n, uint64_t n_cap, double *d_scratch,
+                         double *d_sq_out, void *stream);
 
 /* ---- the fused lookup at CHOSEN positions only (new here: the reference recomputes a window on the host, engine.py:151-170).
  * What it is for: a serving loop wants few rows matched against context that is already on the device -- the last token of

@@ -24,7 +24,7 @@ DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 
 OK, ESTATE, EHIP, ENOMEM, ENODEV, EINVAL, ERANGE = 0, -1, -5, -12, -19, -22, -34
 
-ST_BAD_TOKEN, ST_BAD_ID, ST_INDEX_FULL, ST_STAGE_OVERFLOW = 1, 2, 4, 8
+ST_BAD_TOKEN, ST_BAD_ID, ST_INDEX_FULL, ST_STAGE_OVERFLOW, ST_ROWS_OVERFLOW = 1, 2, 4, 8, 16
 
 
 class SconeCfg(C.Structure):
@@ -117,6 +117,15 @@ def grad_merge_scratch(n_a: int, n_b: int) -> int:
     out = _U64(0)
     if lib().scone_grad_merge_scratch(int(n_a), int(n_b), C.byref(out)) != OK:
         raise ValueError("scone_grad_merge_scratch refused its arguments")
+    return int(out.value)
+
+
+def backward_ctx_partial_slots(max_refs: int) -> int:
+    """``scone_backward_ctx_partial_slots``: the most partial slots a plan of ``max_refs`` references can have,
+    ``floor(2 R / (C + 1))``.  Runs without a GPU."""
+    out = _U64(0)
+    if lib().scone_backward_ctx_partial_slots(int(max_refs), C.byref(out)) != OK:
+        raise ValueError("scone_backward_ctx_partial_slots refused its arguments (max_refs must be below 2^32)")
     return int(out.value)
 
 
@@ -232,6 +241,17 @@ SIGNATURES = {
     "scone_grad_merge_rows": (C.c_int, [_P, _P, _P, _U64, _P, _P, _P, _P]),
     "scone_backward_row_ids": (C.c_int, [_P, _P, _P, _U64, _P]),
     "scone_backward_rows_acc": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _U64, _P, _P, _P]),
+    "scone_backward_ctx_partial_slots": (C.c_int, [_U64, C.POINTER(_U64)]),
+    "scone_backward_ctx_create": (C.c_int, [_P, _I64, C.POINTER(_P)]),
+    "scone_backward_ctx_bytes": (C.c_int, [_P, C.POINTER(_U64)]),
+    "scone_backward_ctx_destroy": (None, [_P]),
+    "scone_backward_plan_dn": (C.c_int, [_P, _P, _P, _I32, _I32, _P]),
+    "scone_backward_plan_varlen_dn": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P]),
+    "scone_backward_ctx_counts": (C.c_int, [_P, C.POINTER(_U64), C.POINTER(_U64), _P]),
+    "scone_backward_rows_dn": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _U64, _P, _P]),
+    "scone_opt_step_dn": (C.c_int, [_P, C.POINTER(OptCfg), _P, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "scone_opt_step_lean_dn": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _P, _U64, _P, _P, _P, _P]),
+    "scone_grad_sqnorm_dn": (C.c_int, [_P, _P, _P, _U64, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

@@ -325,22 +325,9 @@ void plan_free(scone_bwd_plan *pl) {
   delete pl;
 }
 
-enum { BWD_SRC_RECT = 0, BWD_SRC_PACKED = 1, BWD_SRC_CSR = 2 };
-
-struct plan_src {
-  int kind;
-  const int32_t *tok;
-  int32_t B, T;            // rectangle
-  const int32_t *cu;       // packed
-  int32_t n_seqs;
-  const int32_t *offsets;  // CSR
-  const int32_t *ids;
-  long long csr_total;
-};
-
 // Everything after the argument checks.  `max_refs` is the most references the batch can have; the caller's lists are counted
 // here first (their clamped ranges may overlap, so d_offsets[ntok] bounds nothing) and max_refs becomes the owned count.
-int plan_build(scone_handle *h, scone_bwd_plan *pl, const plan_src &src, unsigned long long max_refs, hipStream_t s) {
+int plan_build(scone_handle *h, scone_bwd_plan *pl, const bwd_plan_src &src, unsigned long long max_refs, hipStream_t s) {
   const long long ntok = pl->ntok;
   SCONE_HIP(h, hipMalloc(&pl->d_meta, sizeof(bwd_meta)));
   SCONE_HIP(h, hipMemsetAsync(pl->d_meta, 0, sizeof(bwd_meta), s));
@@ -370,20 +357,15 @@ int plan_build(scone_handle *h, scone_bwd_plan *pl, const plan_src &src, unsigne
     SCONE_HIP(h, hipStreamSynchronize(s));
     return SCONE_OK;
   }
-  const unsigned long long n_rows = h->cfg.n_rows;
-  const unsigned long long owned = h->cfg.row_end - h->cfg.row_begin;
-  const unsigned long long seg_cap = max_refs < owned ? max_refs : owned;
-  const unsigned long long chunk_cap = max_refs / SCONE_BWD_CHUNK + seg_cap + 1;
-  const unsigned long long multi_cap = max_refs / SCONE_BWD_CHUNK + 1;
-  const uint32_t pad_key = (uint32_t)n_rows;
-  const int end_bit = bits_for(n_rows + 1);
+  const bwd_plan_sizes z = scone_bwd_plan_sizes(h, max_refs);
+  const unsigned long long seg_cap = z.seg_cap;
 
   if (!pl->d_kfull) SCONE_HIP(h, hipMalloc(&pl->d_kfull, (size_t)ntok * 4));
   if (!pl->d_w) SCONE_HIP(h, hipMalloc(&pl->d_w, (size_t)ntok * 4));
   SCONE_HIP(h, hipMalloc(&pl->d_ref_p, (size_t)max_refs * 4));
   SCONE_HIP(h, hipMalloc(&pl->d_row_id, (size_t)(seg_cap + 1) * 4));
-  SCONE_HIP(h, hipMalloc(&pl->d_chunks, (size_t)chunk_cap * sizeof(bwd_chunk)));
-  SCONE_HIP(h, hipMalloc(&pl->d_multi, (size_t)multi_cap * sizeof(bwd_multi)));
+  SCONE_HIP(h, hipMalloc(&pl->d_chunks, (size_t)z.chunk_cap * sizeof(bwd_chunk)));
+  SCONE_HIP(h, hipMalloc(&pl->d_multi, (size_t)z.multi_cap * sizeof(bwd_multi)));
 
   tmp_buf ref_off, keys, keys2, vals, flags, incl, seg_start, nch, ch_base, nmulti, multi_base, scratch;
   if (!kown.p) SCONE_HIP(h, kown.alloc((size_t)(ntok + 1) * 4));
@@ -398,91 +380,24 @@ int plan_build(scone_handle *h, scone_bwd_plan *pl, const plan_src &src, unsigne
   SCONE_HIP(h, ch_base.alloc((size_t)(seg_cap + 1) * 4));
   SCONE_HIP(h, nmulti.alloc((size_t)(seg_cap + 1) * 8));
   SCONE_HIP(h, multi_base.alloc((size_t)(seg_cap + 1) * 8));
-  // one scratch for the sort and the four scans
-  size_t need = 0, n1 = 0;
-  SCONE_HIP(h, rocprim::radix_sort_pairs(nullptr, n1, keys.as<uint32_t>(), keys2.as<uint32_t>(), vals.as<uint32_t>(), pl->d_ref_p,
-                                         (size_t)max_refs, 0, end_bit, s));
-  need = n1;
-  SCONE_HIP(h, rocprim::exclusive_scan(nullptr, n1, kown.as<uint32_t>(), ref_off.as<uint32_t>(), 0u, (size_t)(ntok + 1),
-                                       rocprim::plus<uint32_t>(), s));
-  need = n1 > need ? n1 : need;
-  SCONE_HIP(h, rocprim::inclusive_scan(nullptr, n1, flags.as<uint32_t>(), incl.as<uint32_t>(), (size_t)max_refs,
-                                       rocprim::plus<uint32_t>(), s));
-  need = n1 > need ? n1 : need;
-  SCONE_HIP(h, rocprim::exclusive_scan(nullptr, n1, nch.as<uint32_t>(), ch_base.as<uint32_t>(), 0u, (size_t)(seg_cap + 1),
-                                       rocprim::plus<uint32_t>(), s));
-  need = n1 > need ? n1 : need;
-  SCONE_HIP(h, rocprim::exclusive_scan(nullptr, n1, nmulti.as<unsigned long long>(), multi_base.as<unsigned long long>(), 0ull,
-                                       (size_t)(seg_cap + 1), rocprim::plus<unsigned long long>(), s));
-  need = n1 > need ? n1 : need;
+  size_t need = 0;  // one scratch for the sort and the four scans
+  SCONE_TRY(scone_bwd_plan_scratch(h, ntok, z, s, &need));
   SCONE_HIP(h, scratch.alloc(need));
 
-  // (1) id lists -> K_own / K_full / w per position, the reference offsets, the (row, p) pairs in (p, k) order
-  if (src.kind == BWD_SRC_CSR) {  // counted above
-    n1 = need;
-    SCONE_HIP(h, rocprim::exclusive_scan(scratch.p, n1, kown.as<uint32_t>(), ref_off.as<uint32_t>(), 0u, (size_t)(ntok + 1),
-                                         rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL(k_bwd_expand_csr, dim3(blocks_for(ntok)), dim3(BWD_THREADS), 0, s, src.offsets, src.ids, ntok, src.csr_total,
-                       (long long)n_rows, (long long)h->cfg.row_begin, (long long)h->cfg.row_end, ref_off.as<uint32_t>(),
-                       keys.as<uint32_t>(), vals.as<uint32_t>());
-    SCONE_HIP(h, hipGetLastError());
-  } else {
-    // the workspace of THIS stream, held only while the match that writes its records and the kernels that read them are enqueued
-    scone_ws_lock ws(scone_ws_acquire(h, s));
-    if (!ws.w) return scone_fail(h, SCONE_ENOMEM, "scone_backward_plan: out of memory");
-    int rc = scone_ensure_ell(h, ws.w, ntok);
-    if (rc) return rc;
-    if (src.kind == BWD_SRC_RECT)
-      rc = scone_launch_match_ell(h, src.tok, src.B, src.T, ws.w->d_ell, s);
-    else
-      rc = scone_launch_match_ell_varlen(h, src.tok, src.cu, src.n_seqs, ntok, ws.w->d_ell, nullptr, s);
-    if (rc) return rc;
-    const int W = SCONE_ELL_W(h->cfg.max_n);
-    hipLaunchKernelGGL(k_bwd_count_ell, dim3(blocks_for(ntok + 1)), dim3(BWD_THREADS), 0, s, ws.w->d_ell, ntok, W, kown.as<uint32_t>(),
-                       pl->d_kfull, pl->d_w);
-    SCONE_HIP(h, hipGetLastError());
-    n1 = need;
-    SCONE_HIP(h, rocprim::exclusive_scan(scratch.p, n1, kown.as<uint32_t>(), ref_off.as<uint32_t>(), 0u, (size_t)(ntok + 1),
-                                         rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL(k_bwd_expand_ell, dim3(blocks_for(ntok)), dim3(BWD_THREADS), 0, s, ws.w->d_ell, ntok, W, ref_off.as<uint32_t>(),
-                       keys.as<uint32_t>(), vals.as<uint32_t>());
-    SCONE_HIP(h, hipGetLastError());
-  }
-  const uint32_t *ref_total = ref_off.as<uint32_t>() + ntok;
-  hipLaunchKernelGGL(k_bwd_pad, dim3(blocks_for(max_refs)), dim3(BWD_THREADS), 0, s, ref_total, max_refs, pad_key, keys.as<uint32_t>(),
-                     vals.as<uint32_t>());
-  SCONE_HIP(h, hipGetLastError());
-  // (2) stable sort by row: the references of a row stay in (p, k) order
-  n1 = need;
-  SCONE_HIP(h, rocprim::radix_sort_pairs(scratch.p, n1, keys.as<uint32_t>(), keys2.as<uint32_t>(), vals.as<uint32_t>(), pl->d_ref_p,
-                                         (size_t)max_refs, 0, end_bit, s));
-  // (3) segment heads -> U, segment starts, row ids
-  hipLaunchKernelGGL(k_bwd_heads, dim3(blocks_for(max_refs)), dim3(BWD_THREADS), 0, s, keys2.as<uint32_t>(), max_refs, pad_key,
-                     flags.as<uint32_t>());
-  SCONE_HIP(h, hipGetLastError());
-  n1 = need;
-  SCONE_HIP(h, rocprim::inclusive_scan(scratch.p, n1, flags.as<uint32_t>(), incl.as<uint32_t>(), (size_t)max_refs,
-                                       rocprim::plus<uint32_t>(), s));
-  hipLaunchKernelGGL(k_bwd_segs, dim3(blocks_for(max_refs)), dim3(BWD_THREADS), 0, s, keys2.as<uint32_t>(), flags.as<uint32_t>(),
-                     incl.as<uint32_t>(), max_refs, ref_total, seg_start.as<uint32_t>(), pl->d_row_id, pl->d_meta);
-  SCONE_HIP(h, hipGetLastError());
-  // (4) chunk descriptors and the partial slot of every chunk of a row with several
-  hipLaunchKernelGGL(k_bwd_seg_chunks, dim3(blocks_for(seg_cap + 1)), dim3(BWD_THREADS), 0, s, seg_start.as<uint32_t>(), pl->d_meta,
-                     seg_cap, nch.as<uint32_t>(), nmulti.as<unsigned long long>());
-  SCONE_HIP(h, hipGetLastError());
-  n1 = need;
-  SCONE_HIP(h, rocprim::exclusive_scan(scratch.p, n1, nch.as<uint32_t>(), ch_base.as<uint32_t>(), 0u, (size_t)(seg_cap + 1),
-                                       rocprim::plus<uint32_t>(), s));
-  n1 = need;
-  SCONE_HIP(h, rocprim::exclusive_scan(scratch.p, n1, nmulti.as<unsigned long long>(), multi_base.as<unsigned long long>(), 0ull,
-                                       (size_t)(seg_cap + 1), rocprim::plus<unsigned long long>(), s));
-  hipLaunchKernelGGL(k_bwd_fill, dim3(blocks_for(seg_cap)), dim3(BWD_THREADS), 0, s, seg_start.as<uint32_t>(), ch_base.as<uint32_t>(),
-                     multi_base.as<unsigned long long>(), seg_cap, pl->d_meta, pl->d_chunks, pl->d_multi);
-  SCONE_HIP(h, hipGetLastError());
+  bwd_plan_bufs b = {};
+  b.kfull = pl->d_kfull, b.w = pl->d_w, b.ref_p = pl->d_ref_p, b.row_id = pl->d_row_id, b.chunks = pl->d_chunks, b.multi = pl->d_multi;
+  b.meta = pl->d_meta;
+  b.kown = kown.as<uint32_t>(), b.ref_off = ref_off.as<uint32_t>();
+  b.keys = keys.as<uint32_t>(), b.keys2 = keys2.as<uint32_t>(), b.vals = vals.as<uint32_t>();
+  b.flags = flags.as<uint32_t>(), b.incl = incl.as<uint32_t>(), b.seg_start = seg_start.as<uint32_t>();
+  b.nch = nch.as<uint32_t>(), b.ch_base = ch_base.as<uint32_t>();
+  b.nmulti = nmulti.as<unsigned long long>(), b.multi_base = multi_base.as<unsigned long long>();
+  b.scratch = scratch.p, b.scratch_bytes = need;
+  SCONE_TRY(scone_bwd_plan_enqueue(h, src, ntok, z, b, s));
   // the one synchronisation: U, the reference count, and what sizes the partials buffer
   SCONE_HIP(h, hipMemcpyAsync(&pl->m, pl->d_meta, sizeof(bwd_meta), hipMemcpyDeviceToHost, s));
   SCONE_HIP(h, hipStreamSynchronize(s));
-  if (pl->m.n_chunks > chunk_cap || pl->m.n_multi > multi_cap || pl->m.n_segs > seg_cap)
+  if (pl->m.n_chunks > z.chunk_cap || pl->m.n_multi > z.multi_cap || pl->m.n_segs > seg_cap)
     return scone_fail(h, SCONE_ESTATE, "scone_backward_plan: inconsistent plan");
   if (pl->m.n_slots) SCONE_HIP(h, hipMalloc(&pl->d_partial, (size_t)pl->m.n_slots * pl->dim * sizeof(float)));
   return SCONE_OK;
@@ -516,11 +431,6 @@ scone_bwd_plan *plan_new(scone_handle *h, long long ntok) {
   return pl;
 }
 
-unsigned long long cand_per_token(const scone_handle *h) {
-  if (h->cfg.lookup_mode == SCONE_MODE_LONGEST_SUFFIX) return 1;
-  return (unsigned long long)h->cfg.max_n * (h->cfg.max_n + 1) / 2;
-}
-
 template <int DT, bool MEAN>
 void launch_chunks_nt(const scone_bwd_plan *pl, const void *g, float *grad_rows, hipStream_t s) {
   static constexpr int E = DT == SCONE_DT_F32 ? 4 : 8;  // elements of a 16-byte piece of grad_out: the column tile is chosen from it
@@ -551,6 +461,118 @@ void launch_chunks(const scone_bwd_plan *pl, const void *g, int reduce, float *g
 
 }  // namespace
 
+// ---------------------------------------------------------------- the build both plan forms share (scone_bwd_plan.h)
+unsigned long long scone_bwd_cand_per_token(const scone_handle *h) {
+  if (h->cfg.lookup_mode == SCONE_MODE_LONGEST_SUFFIX) return 1;
+  return (unsigned long long)h->cfg.max_n * (h->cfg.max_n + 1) / 2;
+}
+
+bwd_plan_sizes scone_bwd_plan_sizes(const scone_handle *h, unsigned long long max_refs) {
+  bwd_plan_sizes z;
+  const unsigned long long owned = h->cfg.row_end - h->cfg.row_begin;
+  z.max_refs = max_refs;
+  z.seg_cap = max_refs < owned ? max_refs : owned;
+  z.chunk_cap = max_refs / SCONE_BWD_CHUNK + z.seg_cap + 1;
+  z.multi_cap = max_refs / SCONE_BWD_CHUNK + 1;
+  z.end_bit = bits_for(h->cfg.n_rows + 1);
+  return z;
+}
+
+int scone_bwd_plan_scratch(scone_handle *h, long long ntok, const bwd_plan_sizes &z, hipStream_t s, size_t *need_out) {
+  uint32_t *u = nullptr;
+  unsigned long long *ull = nullptr;
+  size_t need = 0, n1 = 0;
+  SCONE_HIP(h, rocprim::radix_sort_pairs(nullptr, n1, u, u, u, u, (size_t)z.max_refs, 0, z.end_bit, s));
+  need = n1;
+  SCONE_HIP(h, rocprim::exclusive_scan(nullptr, n1, u, u, 0u, (size_t)(ntok + 1), rocprim::plus<uint32_t>(), s));
+  need = n1 > need ? n1 : need;
+  SCONE_HIP(h, rocprim::inclusive_scan(nullptr, n1, u, u, (size_t)z.max_refs, rocprim::plus<uint32_t>(), s));
+  need = n1 > need ? n1 : need;
+  SCONE_HIP(h, rocprim::exclusive_scan(nullptr, n1, u, u, 0u, (size_t)(z.seg_cap + 1), rocprim::plus<uint32_t>(), s));
+  need = n1 > need ? n1 : need;
+  SCONE_HIP(h, rocprim::exclusive_scan(nullptr, n1, ull, ull, 0ull, (size_t)(z.seg_cap + 1), rocprim::plus<unsigned long long>(), s));
+  need = n1 > need ? n1 : need;
+  *need_out = need;
+  return SCONE_OK;
+}
+
+int scone_bwd_plan_enqueue(scone_handle *h, const bwd_plan_src &src, long long ntok, const bwd_plan_sizes &z, const bwd_plan_bufs &b,
+                           hipStream_t s) {
+  const unsigned long long n_rows = h->cfg.n_rows, max_refs = z.max_refs, seg_cap = z.seg_cap;
+  const uint32_t pad_key = (uint32_t)n_rows;
+  const size_t need = b.scratch_bytes;
+  size_t n1;
+  // (1) id lists -> K_own / K_full / w per position, the reference offsets, the (row, p) pairs in (p, k) order
+  if (src.kind == BWD_SRC_CSR) {  // counted by the caller
+    n1 = need;
+    SCONE_HIP(h, rocprim::exclusive_scan(b.scratch, n1, b.kown, b.ref_off, 0u, (size_t)(ntok + 1), rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_bwd_expand_csr, dim3(blocks_for(ntok)), dim3(BWD_THREADS), 0, s, src.offsets, src.ids, ntok, src.csr_total,
+                       (long long)n_rows, (long long)h->cfg.row_begin, (long long)h->cfg.row_end, b.ref_off, b.keys, b.vals);
+    SCONE_HIP(h, hipGetLastError());
+  } else {
+    // the workspace of THIS stream, held only while the match that writes its records and the kernels that read them are
+    // enqueued -- unless the records have a buffer of their own
+    scone_ws_lock ws(b.ell ? nullptr : scone_ws_acquire(h, s));
+    int32_t *ell = b.ell;
+    if (!ell) {
+      if (!ws.w) return scone_fail(h, SCONE_ENOMEM, "scone_backward_plan: out of memory");
+      SCONE_TRY(scone_ensure_ell(h, ws.w, ntok));
+      ell = ws.w->d_ell;
+    }
+    int rc;
+    if (src.kind == BWD_SRC_RECT)
+      rc = scone_launch_match_ell(h, src.tok, src.B, src.T, ell, s);
+    else
+      rc = scone_launch_match_ell_varlen(h, src.tok, src.cu, src.n_seqs, ntok, ell, nullptr, s);
+    if (rc) return rc;
+    const int W = SCONE_ELL_W(h->cfg.max_n);
+    hipLaunchKernelGGL(k_bwd_count_ell, dim3(blocks_for(ntok + 1)), dim3(BWD_THREADS), 0, s, ell, ntok, W, b.kown, b.kfull, b.w);
+    SCONE_HIP(h, hipGetLastError());
+    n1 = need;
+    SCONE_HIP(h, rocprim::exclusive_scan(b.scratch, n1, b.kown, b.ref_off, 0u, (size_t)(ntok + 1), rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_bwd_expand_ell, dim3(blocks_for(ntok)), dim3(BWD_THREADS), 0, s, ell, ntok, W, b.ref_off, b.keys, b.vals);
+    SCONE_HIP(h, hipGetLastError());
+  }
+  const uint32_t *ref_total = b.ref_off + ntok;
+  hipLaunchKernelGGL(k_bwd_pad, dim3(blocks_for(max_refs)), dim3(BWD_THREADS), 0, s, ref_total, max_refs, pad_key, b.keys, b.vals);
+  SCONE_HIP(h, hipGetLastError());
+  // (2) stable sort by row: the references of a row stay in (p, k) order
+  n1 = need;
+  SCONE_HIP(h, rocprim::radix_sort_pairs(b.scratch, n1, b.keys, b.keys2, b.vals, b.ref_p, (size_t)max_refs, 0, z.end_bit, s));
+  // (3) segment heads -> U, segment starts, row ids
+  hipLaunchKernelGGL(k_bwd_heads, dim3(blocks_for(max_refs)), dim3(BWD_THREADS), 0, s, b.keys2, max_refs, pad_key, b.flags);
+  SCONE_HIP(h, hipGetLastError());
+  n1 = need;
+  SCONE_HIP(h, rocprim::inclusive_scan(b.scratch, n1, b.flags, b.incl, (size_t)max_refs, rocprim::plus<uint32_t>(), s));
+  hipLaunchKernelGGL(k_bwd_segs, dim3(blocks_for(max_refs)), dim3(BWD_THREADS), 0, s, b.keys2, b.flags, b.incl, max_refs, ref_total,
+                     b.seg_start, b.row_id, b.meta);
+  SCONE_HIP(h, hipGetLastError());
+  // (4) chunk descriptors and the partial slot of every chunk of a row with several
+  hipLaunchKernelGGL(k_bwd_seg_chunks, dim3(blocks_for(seg_cap + 1)), dim3(BWD_THREADS), 0, s, b.seg_start, b.meta, seg_cap, b.nch,
+                     b.nmulti);
+  SCONE_HIP(h, hipGetLastError());
+  n1 = need;
+  SCONE_HIP(h, rocprim::exclusive_scan(b.scratch, n1, b.nch, b.ch_base, 0u, (size_t)(seg_cap + 1), rocprim::plus<uint32_t>(), s));
+  n1 = need;
+  SCONE_HIP(h, rocprim::exclusive_scan(b.scratch, n1, b.nmulti, b.multi_base, 0ull, (size_t)(seg_cap + 1),
+                                       rocprim::plus<unsigned long long>(), s));
+  hipLaunchKernelGGL(k_bwd_fill, dim3(blocks_for(seg_cap)), dim3(BWD_THREADS), 0, s, b.seg_start, b.ch_base, b.multi_base, seg_cap,
+                     b.meta, b.chunks, b.multi);
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}
+
+// Above this many items rocPRIM's radix sort leaves its merge sort for the onesweep kernels, which use a private segment
+// (scratch): the one kind of kernel in a plan that a captured graph is not given (scone_backward_plan_dn refuses the capture).
+unsigned long long scone_bwd_sort_merge_limit() { return rocprim::radix_sort_config<>::merge_sort_limit; }
+
+int scone_bwd_plan_checks(scone_handle *h, const char *who) {
+  if (h->cfg.dim == 0) return scone_refuse(h, SCONE_EINVAL, who, "handle has no table (dim == 0)");
+  if (h->cfg.dim % 8 != 0) return scone_refuse(h, SCONE_EINVAL, who, "needs d % 8 == 0");
+  if (h->cfg.n_rows >= 0xFFFFFFFFull) return scone_refuse(h, SCONE_EINVAL, who, "tables of 2^32 - 1 rows or more are not supported");
+  return SCONE_OK;
+}
+
 extern "C" int scone_backward_chunk(void) { return SCONE_BWD_CHUNK; }
 
 extern "C" int scone_backward_plan(scone_handle *h, const int32_t *d_tok, int32_t B, int32_t T, scone_bwd_plan **out,
@@ -560,13 +582,13 @@ extern "C" int scone_backward_plan(scone_handle *h, const int32_t *d_tok, int32_
   if (B < 0 || T < 0) return scone_fail(h, SCONE_EINVAL, "scone_backward_plan: negative B or T");
   const long long ntok = (long long)B * T;
   if (ntok > 0 && !d_tok) return scone_fail(h, SCONE_EINVAL, "scone_backward_plan: null d_tok");
-  const unsigned long long max_refs = (unsigned long long)ntok * cand_per_token(h);
+  const unsigned long long max_refs = (unsigned long long)ntok * scone_bwd_cand_per_token(h);
   if (ntok > 0x7FFFFFFFll || max_refs >= (1ull << 32))
     return scone_fail(h, SCONE_EINVAL, "scone_backward_plan: too many tokens for one plan (references are numbered in 32 bits)");
   SCONE_ON_DEVICE(h);
   scone_bwd_plan *pl = plan_new(h, ntok);
   if (!pl) return scone_fail(h, SCONE_ENOMEM, "scone_backward_plan: out of memory");
-  plan_src src = {};
+  bwd_plan_src src = {};
   src.kind = BWD_SRC_RECT, src.tok = d_tok, src.B = B, src.T = T;
   return plan_finish(h, pl, plan_build(h, pl, src, max_refs, (hipStream_t)stream), out, h_n_rows, h_n_refs);
 }
@@ -584,13 +606,13 @@ extern "C" int scone_backward_plan_varlen(scone_handle *h, const int32_t *d_tok,
   long long ntok = total_tokens;
   if (n_seqs == 0) ntok = 0;  // as scone_embed_varlen: a batch without sequences is empty
   if (ntok > 0 && (!d_tok || !d_cu_seqlens)) return scone_fail(h, SCONE_EINVAL, "scone_backward_plan_varlen: null pointer");
-  const unsigned long long max_refs = (unsigned long long)ntok * cand_per_token(h);
+  const unsigned long long max_refs = (unsigned long long)ntok * scone_bwd_cand_per_token(h);
   if (max_refs >= (1ull << 32))
     return scone_fail(h, SCONE_EINVAL, "scone_backward_plan_varlen: too many tokens for one plan (references are numbered in 32 bits)");
   SCONE_ON_DEVICE(h);
   scone_bwd_plan *pl = plan_new(h, ntok);
   if (!pl) return scone_fail(h, SCONE_ENOMEM, "scone_backward_plan_varlen: out of memory");
-  plan_src src = {};
+  bwd_plan_src src = {};
   src.kind = BWD_SRC_PACKED, src.tok = d_tok, src.cu = d_cu_seqlens, src.n_seqs = n_seqs;
   return plan_finish(h, pl, plan_build(h, pl, src, max_refs, (hipStream_t)stream), out, h_n_rows, h_n_refs);
 }
@@ -614,7 +636,7 @@ extern "C" int scone_backward_plan_csr(scone_handle *h, const int32_t *d_offsets
   }
   scone_bwd_plan *pl = plan_new(h, ntok);
   if (!pl) return scone_fail(h, SCONE_ENOMEM, "scone_backward_plan_csr: out of memory");
-  plan_src src = {};
+  bwd_plan_src src = {};
   src.kind = BWD_SRC_CSR, src.offsets = d_offsets, src.ids = d_ids, src.csr_total = total;
   return plan_finish(h, pl, plan_build(h, pl, src, (unsigned long long)total, s), out, h_n_rows, h_n_refs);
 }

@@ -51,6 +51,65 @@ struct scone_bwd_plan {
   bwd_meta *d_meta = nullptr;
 };
 
+// ---- one plan build, whoever owns its buffers (scone_backward.hip): scone_backward_plan* allocate them per call and read the
+// totals back; a scone_bwd_ctx (scone_backward_dn.hip) holds them at its worst-case sizes and leaves the totals on the device.
+enum { BWD_SRC_RECT = 0, BWD_SRC_PACKED = 1, BWD_SRC_CSR = 2 };
+
+struct bwd_plan_src {
+  int kind;
+  const int32_t *tok;
+  int32_t B, T;            // rectangle
+  const int32_t *cu;       // packed
+  int32_t n_seqs;
+  const int32_t *offsets;  // CSR
+  const int32_t *ids;
+  long long csr_total;
+};
+
+// what a plan of at most max_refs references can need: all host-known
+struct bwd_plan_sizes {
+  unsigned long long max_refs;   // items sorted and scanned, whatever the batch holds
+  unsigned long long seg_cap;    // most distinct rows: min(max_refs, owned rows)
+  unsigned long long chunk_cap;  // most chunks
+  unsigned long long multi_cap;  // most rows with several chunks
+  int end_bit;                   // the sort's key bits: those of n_rows, the pad key
+};
+
+struct bwd_plan_bufs {
+  // the plan
+  int32_t *kfull;     // [ntok]
+  float *w;           // [ntok]
+  uint32_t *ref_p;    // [max_refs]
+  uint32_t *row_id;   // [seg_cap + 1]
+  bwd_chunk *chunks;  // [chunk_cap]
+  bwd_multi *multi;   // [multi_cap]
+  bwd_meta *meta;     // zeroed by the caller
+  // scratch of the build
+  uint32_t *kown, *ref_off;            // [ntok + 1]
+  uint32_t *keys, *keys2, *vals;       // [max_refs]
+  uint32_t *flags, *incl;              // [max_refs]
+  uint32_t *seg_start;                 // [seg_cap + 2]
+  uint32_t *nch, *ch_base;             // [seg_cap + 1]
+  unsigned long long *nmulti, *multi_base;  // [seg_cap + 1]
+  void *scratch;  // rocPRIM's, scone_bwd_plan_scratch bytes
+  size_t scratch_bytes;
+  int32_t *ell;  // the match records [ntok, SCONE_ELL_W]; null: those of the workspace of the call's stream (token forms)
+};
+
+bwd_plan_sizes scone_bwd_plan_sizes(const scone_handle *h, unsigned long long max_refs);
+// the bytes the sort and the four scans of a build need at most (host only: no device work)
+int scone_bwd_plan_scratch(scone_handle *h, long long ntok, const bwd_plan_sizes &z, hipStream_t s, size_t *need);
+// enqueues the whole build on s: no allocation but the workspace's (b.ell == null), no synchronisation.  ntok > 0, max_refs > 0.
+// The CSR form's kown / kfull / w are counted by the caller (it needs the owned count first).
+int scone_bwd_plan_enqueue(scone_handle *h, const bwd_plan_src &src, long long ntok, const bwd_plan_sizes &z, const bwd_plan_bufs &b,
+                           hipStream_t s);
+// references a position can have: max_n (max_n + 1) / 2, or 1 in longest_suffix mode
+unsigned long long scone_bwd_cand_per_token(const scone_handle *h);
+// the largest sort that stays with rocPRIM's merge sort (no kernel with a private segment)
+unsigned long long scone_bwd_sort_merge_limit();
+// plan_common_checks' refusals for entry point `who`
+int scone_bwd_plan_checks(scone_handle *h, const char *who);
+
 // 16 bytes of grad_out as fp32: 4 elements (fp32) or 8 (fp16 / bf16); every conversion is exact
 template <int DT>
 struct bwd_piece {

@@ -26,6 +26,7 @@
 #define SCONE_ST_BAD_ID 2u
 #define SCONE_ST_INDEX_FULL 4u
 #define SCONE_ST_STAGE_OVERFLOW 8u
+#define SCONE_ST_ROWS_OVERFLOW 16u  // scone_backward_rows_dn: the plan has more rows than the caller's buffers
 
 // ---------------------------------------------------------------- hash index
 // 16-byte slot.  lo/ext hold the exact packed key (no fingerprints, so a probe

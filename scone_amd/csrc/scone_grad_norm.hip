@@ -29,8 +29,10 @@ __device__ __forceinline__ double gn_add_sq(double a, const float4 &g) {
 }
 
 // Q_r: one wave per row; a piece the lane does not have is all +0.0f, and a + (+0.0 * +0.0) keeps every bit of a (a is never -0.0)
-__global__ __launch_bounds__(256) void k_grad_row_sq(const float *__restrict__ grad, unsigned long long n, int d,
-                                                     double *__restrict__ row_sq) {
+// NSRC (scone_opt_rows.h): n by value, or the count scone_grad_sqnorm_dn reads from the device
+template <typename NSRC>
+__global__ __launch_bounds__(256) void k_grad_row_sq(const float *__restrict__ grad, NSRC nsrc, int d, double *__restrict__ row_sq) {
+  const unsigned long long n = nsrc.get();
   const int lane = threadIdx.x & 63;
   const int pieces = d >> 2;
   const unsigned long long nwaves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
@@ -66,9 +68,12 @@ __device__ __forceinline__ double gn_tree(double b, double *lds) {
 }
 
 // P_k: the row sums of tile k; thread t adds rows 1024k + t + 256i, i = 0 .. 3, in range
-__global__ __launch_bounds__(GN_THREADS) void k_grad_tile_sq(const double *__restrict__ row_sq, unsigned long long n,
-                                                             unsigned long long n_tiles, double *__restrict__ tile_sq) {
+// (scone_grad_sqnorm_dn: the tiles are those of n_cap rows; one past n adds nothing and is stored as +0.0)
+template <typename NSRC>
+__global__ __launch_bounds__(GN_THREADS) void k_grad_tile_sq(const double *__restrict__ row_sq, NSRC nsrc, unsigned long long n_tiles,
+                                                             double *__restrict__ tile_sq) {
   __shared__ double lds[GN_THREADS];
+  const unsigned long long n = nsrc.get();
   for (unsigned long long k = blockIdx.x; k < n_tiles; k += gridDim.x) {
     double b = 0.0;
 #pragma unroll
@@ -132,11 +137,37 @@ extern "C" int scone_grad_sqnorm(scone_handle *h, const float *d_grad_rows, uint
   if (n > 0) {
     unsigned blocks = scone_capped_blocks((n + 3) / 4);  // a wave per row, capped as scone_opt_step's grid is
     if (h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks) blocks = (unsigned)h->opt_max_blocks;
-    hipLaunchKernelGGL(k_grad_row_sq, dim3(blocks), dim3(256), 0, s, d_grad_rows, (unsigned long long)n, h->cfg.dim, d_scratch);
-    hipLaunchKernelGGL(k_grad_tile_sq, dim3(scone_capped_blocks(tiles)), dim3(GN_THREADS), 0, s, d_scratch, (unsigned long long)n, tiles,
-                       d_scratch + n);
+    hipLaunchKernelGGL(k_grad_row_sq<opt_n_value>, dim3(blocks), dim3(256), 0, s, d_grad_rows, opt_n_value{n}, h->cfg.dim, d_scratch);
+    hipLaunchKernelGGL(k_grad_tile_sq<opt_n_value>, dim3(scone_capped_blocks(tiles)), dim3(GN_THREADS), 0, s, d_scratch, opt_n_value{n},
+                       tiles, d_scratch + n);
   }
   hipLaunchKernelGGL(k_grad_total_sq, dim3(1), dim3(GN_THREADS), 0, s, d_scratch ? d_scratch + n : nullptr, tiles, d_sq_out);
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}
+
+extern "C" int scone_grad_sqnorm_dn(scone_handle *h, const float *d_grad_rows, const uint64_t *d_n, uint64_t n_cap, double *d_scratch,
+                                    double *d_sq_out, scone_stream_t stream) {
+  const char *who = "scone_grad_sqnorm_dn";
+  if (!h) return SCONE_EINVAL;
+  if (h->cfg.dim == 0) return scone_refuse(h, SCONE_EINVAL, who, "handle has no table (dim == 0)");
+  if (h->cfg.dim % 4 != 0) return scone_refuse(h, SCONE_EINVAL, who, "dim must be a multiple of 4 (rows are read in 16-byte pieces)");
+  if (!d_sq_out) return scone_refuse(h, SCONE_EINVAL, who, "null d_sq_out");
+  if (!d_n) return scone_refuse(h, SCONE_EINVAL, who, "null d_n");
+  if (n_cap > 0 && (!d_grad_rows || !d_scratch))
+    return scone_refuse(h, SCONE_EINVAL, who, "null pointer (d_grad_rows and d_scratch are needed when n_cap > 0)");
+  SCONE_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  const opt_n_device nsrc{reinterpret_cast<const unsigned long long *>(d_n), n_cap};
+  const unsigned long long tiles = gn_tiles(n_cap);  // every tile of the capacity: those past n hold +0.0
+  if (n_cap > 0) {
+    unsigned blocks = scone_capped_blocks((n_cap + 3) / 4);  // a wave per row, capped as scone_opt_step's grid is
+    if (h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks) blocks = (unsigned)h->opt_max_blocks;
+    hipLaunchKernelGGL(k_grad_row_sq<opt_n_device>, dim3(blocks), dim3(256), 0, s, d_grad_rows, nsrc, h->cfg.dim, d_scratch);
+    hipLaunchKernelGGL(k_grad_tile_sq<opt_n_device>, dim3(scone_capped_blocks(tiles)), dim3(GN_THREADS), 0, s, d_scratch, nsrc, tiles,
+                       d_scratch + n_cap);
+  }
+  hipLaunchKernelGGL(k_grad_total_sq, dim3(1), dim3(GN_THREADS), 0, s, d_scratch ? d_scratch + n_cap : nullptr, tiles, d_sq_out);
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
 }

@@ -52,10 +52,11 @@ __device__ __forceinline__ void opt_elem(const scone_opt_scalars &k, float g, fl
   }
 }
 
-// One wave per listed row; the grid-stride loop over rows is k_store_f32's.
-template <int FMT, int KIND>
+// One wave per listed row; the grid-stride loop over rows is k_store_f32's.  NSRC (scone_opt_rows.h): n by value, or the count
+// scone_opt_step_dn reads from the device.
+template <int FMT, int KIND, typename NSRC>
 __global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ ids, const float *__restrict__ grad,
-                                                  unsigned long long n, unsigned long long row_begin, unsigned long long row_end,
+                                                  NSRC nsrc, unsigned long long row_begin, unsigned long long row_end,
                                                   int d, scone_opt_scalars sc, float *__restrict__ master, float *__restrict__ state1,
                                                   float *__restrict__ state2, scone_row_store st, __half *__restrict__ scales,
                                                   uint32_t *__restrict__ status, const scone_grad_ctl *__restrict__ ctl) {
@@ -65,6 +66,7 @@ __global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ id
     if (ctl->skip != 0u) return;
     sc.gscale = opt_uniform(sc.gscale * ctl->coef);
   }
+  const unsigned long long n = nsrc.get();
   constexpr bool HAS_M = KIND == SCONE_OPT_ADAM;
   constexpr bool HAS_V = KIND != SCONE_OPT_SGD;
   const int lane = threadIdx.x & 63;
@@ -159,13 +161,19 @@ struct opt_args {
   scone_opt_scalars sc;
   float *master, *s1, *s2;
   const scone_grad_ctl *ctl;  // null: scone_opt_step
+  const unsigned long long *d_n;  // scone_opt_step_dn: the count on the device, n its cap; null: n by value
 };
 
 template <int FMT, int KIND>
 void opt_launch(scone_handle *h, const opt_args &a, unsigned blocks, hipStream_t s) {
-  hipLaunchKernelGGL((k_opt_step<FMT, KIND>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, a.n, (unsigned long long)h->cfg.row_begin,
-                     (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2, scone_store_of(h),
-                     (__half *)h->scales, h->d_status, a.ctl);
+  if (a.d_n)
+    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_device>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, opt_n_device{a.d_n, a.n},
+                       (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2,
+                       scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
+  else
+    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, opt_n_value{a.n},
+                       (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2,
+                       scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
 }
 
 template <int FMT>
@@ -188,11 +196,13 @@ extern "C" int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars 
 
 namespace {
 
-// scone_opt_step (with_ctl false, ctl null) and scone_opt_step_ctl
+// scone_opt_step (with_ctl false, ctl null), scone_opt_step_ctl and scone_opt_step_dn (with_n: n is the cap of *d_n)
 int opt_step(scone_handle *h, const char *who, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
-             float *d_master, float *d_state1, float *d_state2, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream) {
+             float *d_master, float *d_state1, float *d_state2, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream,
+             bool with_n = false, const uint64_t *d_n = nullptr) {
   SCONE_TRY(opt_need_table(h, who, opt_check(cfg)));
   if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
+  if (with_n && !d_n) return scone_refuse(h, SCONE_EINVAL, who, "null d_n");
   if (n == 0) return SCONE_OK;
   if (!d_row_ids || !d_grad_rows || !d_master) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
   if (cfg->kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, who, "Adam needs d_state1 (m)");
@@ -200,6 +210,7 @@ int opt_step(scone_handle *h, const char *who, const scone_opt_cfg *cfg, const i
   SCONE_ON_DEVICE(h);
   opt_args a;
   a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2, a.ctl = d_ctl;
+  a.d_n = reinterpret_cast<const unsigned long long *>(d_n);
   opt_scalars(cfg, &a.sc);
   const unsigned blocks = opt_begin(h, n);
   const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch_kind<decltype(F)::value>(h, cfg->kind, a, blocks, (hipStream_t)stream); });
@@ -219,4 +230,10 @@ extern "C" int scone_opt_step_ctl(scone_handle *h, const scone_opt_cfg *cfg, con
                                   uint64_t n, float *d_master, float *d_state1, float *d_state2, const scone_grad_ctl *d_ctl,
                                   scone_stream_t stream) {
   return opt_step(h, "scone_opt_step_ctl", cfg, d_row_ids, d_grad_rows, n, d_master, d_state1, d_state2, true, d_ctl, stream);
+}
+
+extern "C" int scone_opt_step_dn(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                                 const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_state1, float *d_state2,
+                                 const scone_grad_ctl *d_ctl, scone_stream_t stream) {
+  return opt_step(h, "scone_opt_step_dn", cfg, d_row_ids, d_grad_rows, n_cap, d_master, d_state1, d_state2, false, d_ctl, stream, true, d_n);
 }

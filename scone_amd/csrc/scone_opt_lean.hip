@@ -17,9 +17,10 @@
 
 namespace {
 
-template <int FMT, int KIND, bool INPLACE, bool STOCH>
+// NSRC (scone_opt_rows.h): n by value, or the count scone_opt_step_lean_dn reads from the device
+template <int FMT, int KIND, bool INPLACE, bool STOCH, typename NSRC>
 __global__ __launch_bounds__(256) void k_opt_lean(const int64_t *__restrict__ ids, const float *__restrict__ grad,
-                                                  unsigned long long n, unsigned long long row_begin, unsigned long long row_end,
+                                                  NSRC nsrc, unsigned long long row_begin, unsigned long long row_end,
                                                   int d, scone_opt_scalars sc, lean_rand rnd, float *__restrict__ master,
                                                   float *__restrict__ row_state, scone_row_store st, __half *__restrict__ scales,
                                                   uint32_t *__restrict__ status, const scone_grad_ctl *__restrict__ ctl) {
@@ -29,6 +30,7 @@ __global__ __launch_bounds__(256) void k_opt_lean(const int64_t *__restrict__ id
     if (ctl->skip != 0u) return;
     sc.gscale = opt_uniform(sc.gscale * ctl->coef);
   }
+  const unsigned long long n = nsrc.get();
   static_assert(!INPLACE || FMT == SCONE_FMT_F32 || FMT == SCONE_FMT_BF16, "only fp32 and bf16 rows are weights in place");
   static_assert(!STOCH || (INPLACE && FMT == SCONE_FMT_BF16), "only an in-place bf16 row is rounded");
   constexpr bool ROWWISE = KIND == SCONE_LEAN_ROWWISE_ADAGRAD;
@@ -146,13 +148,19 @@ struct lean_args {
   lean_rand rnd;
   float *master, *row_state;
   const scone_grad_ctl *ctl;  // null: scone_opt_step_lean
+  const unsigned long long *d_n;  // scone_opt_step_lean_dn: the count on the device, n its cap; null: n by value
 };
 
 template <int FMT, int KIND, bool INPLACE, bool STOCH>
 void lean_launch(scone_handle *h, const lean_args &a, unsigned blocks, hipStream_t s) {
-  hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, a.n,
-                     (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.rnd, a.master,
-                     a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
+  if (a.d_n)
+    hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH, opt_n_device>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
+                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc,
+                       a.rnd, a.master, a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
+  else
+    hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH, opt_n_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
+                       opt_n_value{a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.rnd,
+                       a.master, a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
 }
 
 template <int FMT, bool INPLACE, bool STOCH>
@@ -177,11 +185,13 @@ extern "C" uint32_t scone_lean_rand16(uint64_t seed, int64_t step, uint64_t row_
 
 namespace {
 
-// scone_opt_step_lean (with_ctl false, ctl null) and scone_opt_step_lean_ctl
+// scone_opt_step_lean (with_ctl false, ctl null), scone_opt_step_lean_ctl and scone_opt_step_lean_dn (with_n: n is the cap of *d_n)
 int opt_step_lean(scone_handle *h, const char *who, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
-                  uint64_t n, float *d_master, float *d_row_state, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream) {
+                  uint64_t n, float *d_master, float *d_row_state, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream,
+                  bool with_n = false, const uint64_t *d_n = nullptr) {
   SCONE_TRY(opt_need_table(h, who, lean_check(cfg)));
   if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
+  if (with_n && !d_n) return scone_refuse(h, SCONE_EINVAL, who, "null d_n");
   const int fmt = h->cfg.table_fmt;
   const bool inplace = d_master == nullptr, stoch = cfg->rounding == SCONE_ROUND_STOCHASTIC;
   if (inplace && fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
@@ -198,6 +208,7 @@ int opt_step_lean(scone_handle *h, const char *who, const scone_lean_cfg *cfg, c
   SCONE_ON_DEVICE(h);
   lean_args a;
   a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state, a.ctl = d_ctl;
+  a.d_n = reinterpret_cast<const unsigned long long *>(d_n);
   a.rnd.seed = cfg->seed, a.rnd.step = cfg->step;
   lean_scalars(cfg, &a.sc);
   const unsigned blocks = opt_begin(h, n);
@@ -227,4 +238,11 @@ extern "C" int scone_opt_step_lean_ctl(scone_handle *h, const scone_lean_cfg *cf
                                        uint64_t n, float *d_master, float *d_row_state, const scone_grad_ctl *d_ctl,
                                        scone_stream_t stream) {
   return opt_step_lean(h, "scone_opt_step_lean_ctl", cfg, d_row_ids, d_grad_rows, n, d_master, d_row_state, true, d_ctl, stream);
+}
+
+extern "C" int scone_opt_step_lean_dn(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                                      const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_row_state,
+                                      const scone_grad_ctl *d_ctl, scone_stream_t stream) {
+  return opt_step_lean(h, "scone_opt_step_lean_dn", cfg, d_row_ids, d_grad_rows, n_cap, d_master, d_row_state, false, d_ctl, stream, true,
+                       d_n);
 }

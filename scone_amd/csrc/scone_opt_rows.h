@@ -31,6 +31,22 @@ static inline unsigned opt_begin(scone_handle *h, unsigned long long n) {
   return h->opt_max_blocks > 0 && blocks > (unsigned long long)h->opt_max_blocks ? (unsigned)h->opt_max_blocks : blocks;
 }
 
+// Where a row-parallel kernel takes its row count from.  opt_n_value: the launch, as ever (one 8-byte kernel argument).
+// opt_n_device (the _dn entry points): n = min(*d_n, n_cap), a count an earlier kernel of the stream left on the device; the
+// address is a kernel argument, so the load is a scalar one that every wave makes before anything else.
+struct opt_n_value {
+  unsigned long long n;
+  __device__ __forceinline__ unsigned long long get() const { return n; }
+};
+struct opt_n_device {
+  const unsigned long long *d_n;
+  unsigned long long n_cap;
+  __device__ __forceinline__ unsigned long long get() const {
+    const unsigned long long n = *d_n;
+    return n < n_cap ? n : n_cap;
+  }
+};
+
 // a wave-uniform float computed by the vector unit, put back where a kernel argument lives (a scalar register): the kernels read
 // gscale in every element's statement, and the _ctl entry points replace it by a product
 __device__ __forceinline__ float opt_uniform(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }

@@ -599,6 +599,158 @@ class BackwardPlan:
         return k
 
 
+def _device_count(who: str, n, device: torch.device) -> torch.Tensor:
+    """``n=`` of the ``_dn`` calls: ONE int64 on the table's device (what :meth:`BackwardContext.rows` returns third)."""
+    if not (isinstance(n, torch.Tensor) and n.dtype == torch.int64 and n.numel() == 1 and n.device == device and n.is_contiguous()):
+        raise ValueError(f"{who}: n must be a 1-element int64 tensor on {device} (BackwardContext.rows returns it)")
+    return n
+
+
+class BackwardContext:
+    """``scone_bwd_ctx``: the backward without a host synchronisation (include/scone_hip.h, "backward and optimizer step without
+    a host synchronisation").  Holds, allocated once, every buffer a plan of up to ``max_tokens`` positions can need;
+    :meth:`plan` and :meth:`rows` neither synchronise nor allocate device memory of the library's, so a whole
+    ``plan; rows; opt_step(n=)`` chain can be enqueued while the device is busy, and captured in a ``torch.cuda.graph``.  The
+    counts of the current plan live on the device; :meth:`counts` is the synchronising read.  One plan at a time: a new
+    :meth:`plan` overwrites the previous one (stream order protects work already enqueued on the same stream).  A context
+    manager; ``close()`` frees the device memory.  Made by :meth:`SconeTable.backward_context`."""
+
+    def __init__(self, table: "SconeTable", max_tokens: int) -> None:
+        self._table, self._c = table, None
+        self.max_tokens = int(max_tokens)
+        if self.max_tokens < 0:
+            raise ValueError("backward_context: max_tokens must be >= 0")
+        ctx = C.c_void_p()
+        with torch.cuda.device(table.device):
+            rc = L.lib().scone_backward_ctx_create(table._h, self.max_tokens, C.byref(ctx))
+        table._check(rc, "scone_backward_ctx_create")
+        self._c = ctx
+        self.ntok = 0                             # positions of the current plan (host-known)
+        nbytes = C.c_uint64(0)
+        table._check(L.lib().scone_backward_ctx_bytes(ctx, C.byref(nbytes)), "scone_backward_ctx_bytes")
+        self.nbytes = int(nbytes.value)           # device memory held
+
+    def close(self) -> None:
+        if self._c is not None:
+            L.lib().scone_backward_ctx_destroy(self._c)
+            self._c = None
+
+    def __enter__(self) -> "BackwardContext":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ctx(self):
+        if self._c is None:
+            raise SconeError("BackwardContext is closed")
+        if self._table._h is None:
+            raise SconeError("BackwardContext: its table is closed")
+        return self._c
+
+    def plan(self, tok: torch.Tensor, cu_seqlens=None) -> "BackwardContext":
+        """``scone_backward_plan_dn`` / ``scone_backward_plan_varlen_dn``: plan the batch :meth:`SconeTable.embed`
+        (``tok [B, T]``) or :meth:`SconeTable.embed_varlen` (``tok [total]`` with ``cu_seqlens``) looks up -- the plan
+        :meth:`SconeTable.backward_plan` returns, left in the context.  No synchronisation when ``tok`` (and a device
+        ``cu_seqlens``) are int32, contiguous and on the table's device already; under capture pass such tensors.
+        ``IndexError``: more positions than ``max_tokens``."""
+        ctx, t = self._ctx(), self._table
+        if cu_seqlens is None:
+            tok = t._tok(tok)
+            B, T = tok.shape
+            if B * T > self.max_tokens:
+                raise IndexError(f"BackwardContext.plan: {B * T} positions, the context holds {self.max_tokens}")
+            with torch.cuda.device(t.device):
+                stream = torch.cuda.current_stream(t.device).cuda_stream
+                rc = L.lib().scone_backward_plan_dn(t._h, ctx, _ptr(tok) if B * T else None, B, T, stream)
+            t._check(rc, "scone_backward_plan_dn")
+            self.ntok, self._keep = B * T, (tok,)
+            return self
+        if tok.dim() != 1:
+            raise ValueError("a packed batch takes its token ids as a 1-D tensor [total]")
+        tok = tok.to(device=t.device, dtype=torch.int32).contiguous()
+        total = tok.shape[0]
+        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+            if not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                    and cu_seqlens.numel() >= 1):
+                raise ValueError("a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+            cu = cu_seqlens
+        else:
+            cu = torch.from_numpy(check_cu_seqlens(cu_seqlens, total)).to(t.device)
+        ntok = total if cu.numel() > 1 else 0
+        if ntok > self.max_tokens:
+            raise IndexError(f"BackwardContext.plan: {ntok} positions, the context holds {self.max_tokens}")
+        with torch.cuda.device(t.device):
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            rc = L.lib().scone_backward_plan_varlen_dn(t._h, ctx, _ptr(tok) if total else None, _ptr(cu), cu.numel() - 1, total, stream)
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"scone_backward_plan_varlen_dn: {L.lib().scone_last_error(t._h).decode()} "
+                                       f"[{L.lib().scone_strerror(rc).decode()}]")
+        t._check(rc, "scone_backward_plan_varlen_dn")
+        self.ntok, self._keep = ntok, (tok, cu)
+        return self
+
+    def rows_cap(self) -> int:
+        """The most rows the current plan can have on the host's knowledge: ``min(ntok * candidates, owned rows)``."""
+        t = self._table
+        cand = 1 if t.lookup_mode == "longest_suffix" else t.max_n * (t.max_n + 1) // 2
+        return min(self.ntok * cand, t.row_end - t.row_begin)
+
+    def rows(self, grad_out: torch.Tensor, reduce: str = "mean", out=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``scone_backward_rows_dn``: ``(ids_buf, rows_buf, n)`` -- the first ``n`` entries of ``ids_buf`` (int64) and rows of
+        ``rows_buf`` (fp32 ``[cap, d]``) are, bit for bit, what :meth:`BackwardPlan.rows` returns for the same batch; ``n`` is a
+        1-element int64 tensor ON THE DEVICE (``U``), the ``n=`` of :meth:`SconeTable.opt_step`, :meth:`SconeTable.opt_step_lean`
+        and :meth:`SconeTable.grad_sqnorm`.  ``out = (ids_buf, rows_buf)`` or ``(ids_buf, rows_buf, n)``: the caller's buffers
+        (``None``: fresh ones of :meth:`rows_cap` rows).  Entries past ``n`` are not touched.  A plan of more rows than the
+        buffers hold writes nothing, sets ``n = 0`` and raises status bit 4 (:meth:`SconeTable.status`).  No synchronisation."""
+        ctx, t = self._ctx(), self._table
+        if grad_out.dtype not in _DT:
+            raise ValueError(f"grad_out must be fp32, fp16 or bf16, not {grad_out.dtype}")
+        if grad_out.numel() != self.ntok * t.dim or (grad_out.dim() and grad_out.shape[-1] != t.dim and grad_out.numel()):
+            raise ValueError(f"grad_out must hold [{self.ntok}, {t.dim}] elements, got {tuple(grad_out.shape)}")
+        if reduce not in _REDUCE:
+            raise ValueError(f"unknown reduce {reduce!r}")
+        if not (grad_out.is_cuda and grad_out.device == t.device and grad_out.is_contiguous()):
+            grad_out = grad_out.to(device=t.device).contiguous()
+        n = None
+        if out is None:
+            cap = self.rows_cap()
+            ids = torch.empty(cap, dtype=torch.int64, device=t.device)
+            rows = torch.empty((cap, t.dim), dtype=torch.float32, device=t.device)
+        else:
+            ids, rows = out[0], out[1]
+            n = out[2] if len(out) > 2 else None
+            if not (ids.is_cuda and ids.device == t.device and ids.is_contiguous() and ids.dtype == torch.int64 and ids.dim() == 1):
+                raise ValueError(f"BackwardContext.rows: out[0] must be a contiguous int64 [cap] tensor on {t.device}")
+            if not (rows.is_cuda and rows.device == t.device and rows.is_contiguous() and rows.dtype == torch.float32
+                    and rows.dim() == 2 and rows.shape[1] == t.dim):
+                raise ValueError(f"BackwardContext.rows: out[1] must be a contiguous fp32 [cap, {t.dim}] tensor on {t.device}")
+        n = torch.empty(1, dtype=torch.int64, device=t.device) if n is None else _device_count("BackwardContext.rows", n, t.device)
+        cap = min(ids.numel(), rows.shape[0])
+        with torch.cuda.device(t.device):
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            rc = L.lib().scone_backward_rows_dn(t._h, ctx, _ptr(grad_out) if grad_out.numel() else None, _DT[grad_out.dtype],
+                                                _REDUCE[reduce], _ptr(ids) if cap else None, _ptr(rows) if cap else None, cap,
+                                                _ptr(n), stream)
+        t._check(rc, "scone_backward_rows_dn")
+        return ids, rows, n
+
+    def counts(self) -> Tuple[int, int]:
+        """``scone_backward_ctx_counts``: ``(n_rows, n_refs)`` of the current plan.  SYNCHRONISES the current stream."""
+        ctx, t = self._ctx(), self._table
+        n_rows, n_refs = C.c_uint64(0), C.c_uint64(0)
+        with torch.cuda.device(t.device):
+            rc = L.lib().scone_backward_ctx_counts(ctx, C.byref(n_rows), C.byref(n_refs), torch.cuda.current_stream(t.device).cuda_stream)
+        t._check(rc, "scone_backward_ctx_counts")
+        return int(n_rows.value), int(n_refs.value)
+
+
 class SconeTable:
     """Device-resident f-gram index (+ optional table shard)."""
 
@@ -617,6 +769,7 @@ class SconeTable:
         self.fmt = format_code(table_format)
         self.row_begin = int(row_begin)
         self.row_end = int(n_rows if row_end is None else row_end)
+        self.lookup_mode = str(lookup_mode)
         cfg = L.SconeCfg(C.sizeof(L.SconeCfg), self.device.index, self.max_n, self.dim, self.fmt,
                          _PLACE[placement], self.n_rows, self.row_begin, self.row_end, int(index_capacity),
                          int(hot_rows), _MODE[lookup_mode], int(stage_tokens), int(cache_rows))
@@ -1116,6 +1269,17 @@ class SconeTable:
                                                 C.byref(n_rows), C.byref(n_refs), stream)
         return self._make_plan(rc, "scone_backward_plan_varlen", plan, total if cu.numel() > 1 else 0, n_rows, n_refs)
 
+    def backward_context(self, max_tokens: int) -> BackwardContext:
+        """``scone_backward_ctx_create``: a :class:`BackwardContext` for batches of up to ``max_tokens`` positions -- the
+        backward whose plan and counts stay on the device (no synchronisation, no allocation per step; capturable).
+        Allocates (and so synchronises) once, here; ``.nbytes`` reports the device memory held."""
+        return BackwardContext(self, max_tokens)
+
+    def rows_overflowed(self) -> bool:
+        """Reads and CLEARS the sticky status bits (as :meth:`status`; synchronises) and tells whether bit 4 was set: a
+        :meth:`BackwardContext.rows` found more rows than its buffers hold, wrote none and left ``n = 0``."""
+        return bool(self.status() & L.ST_ROWS_OVERFLOW)
+
     def backward_plan_csr(self, offsets: torch.Tensor, ids: torch.Tensor) -> BackwardPlan:
         """``scone_backward_plan_csr``: the plan of the caller's id lists (``offsets [ntok + 1]``, ``ids``), the counterpart
         of :meth:`gather_reduce`.  Host ``offsets`` are checked here: ``offsets[-1]`` (the library reads no id at or beyond it)
@@ -1214,39 +1378,55 @@ class SconeTable:
         m = self.grad_merge_map(ids_a, ids_b)
         return m.ids, self.grad_merge_rows(m, rows_a, rows_b)
 
-    def grad_sqnorm(self, grad_rows: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def grad_sqnorm(self, grad_rows: torch.Tensor, scratch: Optional[torch.Tensor] = None, *, n: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``scone_grad_sqnorm``: the squared norm of ``grad_rows`` (fp32 ``[U, d]``, what :meth:`BackwardPlan.rows` returns),
         summed in double in the fixed order of include/scone_hip.h, "gradient norm, clipping and skipped steps".  Returns
         ``(sq, row_sq)``: a 0-dim float64 device tensor and the per-row squared norms, a float64 ``[U]`` view of the call's
         scratch.  ``scratch``: a contiguous float64 device tensor of at least ``_lib.grad_sqnorm_scratch(U)`` elements to use
         instead of a fresh one (the tile sums follow the row sums in it).  At most three launches on the current stream; no
-        synchronisation."""
+        synchronisation.  ``n`` (a 1-element int64 device tensor, :meth:`BackwardContext.rows`' third result):
+        ``scone_grad_sqnorm_dn`` -- the norm of the first ``min(n, U)`` rows, ``U`` now the capacity; the same bits.  ``out``: a
+        0-dim float64 device tensor to write ``sq`` to instead of a fresh one."""
         if grad_rows.dim() != 2 or grad_rows.shape[1] != self.dim or grad_rows.dtype != torch.float32:
             raise ValueError(f"grad_sqnorm: grad_rows must be fp32 [U, {self.dim}], got {grad_rows.dtype} {tuple(grad_rows.shape)}")
         grad_rows = grad_rows.to(device=self.device).contiguous()
-        n = grad_rows.shape[0]
+        n_dev, n = n, grad_rows.shape[0]
         need = L.grad_sqnorm_scratch(n)
         if scratch is None:
             scratch = torch.empty(need, dtype=torch.float64, device=self.device)
         elif not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.numel() >= need
                   and scratch.device == self.device and scratch.is_contiguous()):
             raise ValueError(f"grad_sqnorm: scratch must be a contiguous float64 tensor of at least {need} elements on {self.device}")
-        sq = torch.empty((), dtype=torch.float64, device=self.device)
+        if out is None:
+            sq = torch.empty((), dtype=torch.float64, device=self.device)
+        elif isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.numel() == 1 and out.device == self.device:
+            sq = out
+        else:
+            raise ValueError(f"grad_sqnorm: out must be a one-element float64 tensor on {self.device}")
+        if n_dev is not None:
+            n_dev = _device_count("grad_sqnorm", n_dev, self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            rc = L.lib().scone_grad_sqnorm(self._h, _ptr(grad_rows) if n else None, n, _ptr(scratch) if need else None, _ptr(sq),
-                                           stream.cuda_stream)
-        self._check(rc, "scone_grad_sqnorm")
-        if n:
+            if n_dev is None:
+                rc = L.lib().scone_grad_sqnorm(self._h, _ptr(grad_rows) if n else None, n, _ptr(scratch) if need else None, _ptr(sq),
+                                               stream.cuda_stream)
+            else:
+                rc = L.lib().scone_grad_sqnorm_dn(self._h, _ptr(grad_rows) if n else None, _ptr(n_dev), n,
+                                                  _ptr(scratch) if need else None, _ptr(sq), stream.cuda_stream)
+        self._check(rc, "scone_grad_sqnorm" if n_dev is None else "scone_grad_sqnorm_dn")
+        if n and n_dev is None:
             grad_rows.record_stream(stream)                        # it may be a temporary of the caller
         return sq, scratch[:n]
 
-    def grad_ctl(self, terms, grad_scale: float = 1.0, max_norm: Optional[float] = None, skip_nonfinite: bool = False) -> GradCtl:
+    def grad_ctl(self, terms, grad_scale: float = 1.0, max_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 out: Optional[GradCtl] = None) -> GradCtl:
         """``scone_grad_ctl_set``: a :class:`GradCtl` from squared-norm ``terms`` that stay on the device -- a sequence of 0-dim
         tensors (``grad_sqnorm``'s ``sq``, the dense parameters' squared norm, other shards') and floats, or one 1-D tensor; they
         are added in the order given, in double.  ``grad_scale`` is the un-scaling factor the step will use (the norm is that of
         the un-scaled gradient); ``max_norm=None`` does not clip; ``skip_nonfinite`` sets the block's ``skip`` when the sum is inf
-        or NaN.  One launch on the current stream; no synchronisation."""
+        or NaN.  One launch on the current stream; no synchronisation.  ``out``: a :class:`GradCtl` to fill instead of a fresh one
+        (a captured step keeps one)."""
         if not isinstance(terms, torch.Tensor):
             terms = list(terms)
         if isinstance(terms, torch.Tensor):
@@ -1259,27 +1439,31 @@ class SconeTable:
         else:
             vec = torch.zeros(0, dtype=torch.float64, device=self.device)
         vec = vec.contiguous()
-        ctl = GradCtl(self.device)
+        ctl = GradCtl(self.device) if out is None else out
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             rc = L.lib().scone_grad_ctl_set(self._h, _ptr(vec) if vec.numel() else None, vec.numel(), float(grad_scale),
                                             float("inf") if max_norm is None else float(max_norm), int(bool(skip_nonfinite)),
                                             _ptr(ctl.buf), stream.cuda_stream)
         self._check(rc, "scone_grad_ctl_set")
-        if vec.numel():
+        if vec.numel() and out is None:                            # (out=: the caller keeps the block, and its terms with it)
             vec.record_stream(stream)
         return ctl
 
     def opt_step(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, master: torch.Tensor, *, kind, lr: float, step: int = 1,
                  state1: Optional[torch.Tensor] = None, state2: Optional[torch.Tensor] = None, betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, ctl: Optional["GradCtl"] = None) -> None:
+                 eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, ctl: Optional["GradCtl"] = None,
+                 n: Optional[torch.Tensor] = None) -> None:
         """``scone_opt_step``: the fused sparse optimizer step (include/scone_hip.h, "optimizer step").  ``row_ids`` ``[U]``
         int64 ascending and distinct and ``grad_rows`` ``[U, d]`` fp32 are what :meth:`BackwardPlan.rows` returns.  ``master``,
         ``state1`` (Adam's m) and ``state2`` (Adam's v / Adagrad's sum of squares) are fp32 ``[row_end - row_begin, d]``,
         contiguous, on the table's device: the rows this handle owns, updated in place; the served table receives the updated
         rows in its own format.  ``kind``: ``"sgd"``, ``"adagrad"`` or ``"adam"``.  One kernel launch on the current stream; no
         synchronisation.  ``ctl`` (a :class:`GradCtl`): ``scone_opt_step_ctl`` -- the kernel multiplies ``grad_scale`` by the block's
-        ``coef`` and changes nothing at all when its ``skip`` is set."""
+        ``coef`` and changes nothing at all when its ``skip`` is set.  ``n`` (a 1-element int64 device tensor,
+        :meth:`BackwardContext.rows`' third result): ``scone_opt_step_dn`` -- the step over the first ``min(n, U)`` listed rows,
+        ``U`` now the capacity of the two buffers; the count is read on the device.  Under capture a replay repeats Adam's
+        ``step`` as captured."""
         cfg = _opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step)
         owned = self.row_end - self.row_begin
         for name, t, needed in (("master", master, True), ("state1", state1, cfg.kind == L.OPT_ADAM),
@@ -1299,6 +1483,14 @@ class SconeTable:
             raise ValueError("opt_step: row_ids must be int64 and grad_rows fp32")
         row_ids = row_ids.to(device=self.device).contiguous()
         grad_rows = grad_rows.to(device=self.device).contiguous()
+        if n is not None:
+            n = _device_count("opt_step", n, self.device)
+            with torch.cuda.device(self.device):
+                rc = L.lib().scone_opt_step_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
+                                               _ptr(master), _ptr(state1), _ptr(state2), None if ctl is None else _ptr(ctl.buf),
+                                               torch.cuda.current_stream(self.device).cuda_stream)
+            self._check(rc, "scone_opt_step_dn")
+            return
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             if ctl is None:
@@ -1315,14 +1507,16 @@ class SconeTable:
     def opt_step_lean(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, *, kind, lr: float, master: Optional[torch.Tensor] = None,
                       row_state: Optional[torch.Tensor] = None, eps: float = 1e-10, weight_decay: float = 0.0,
                       grad_scale: float = 1.0, rounding="nearest", seed: int = 0, step: int = 1,
-                      ctl: Optional["GradCtl"] = None) -> None:
+                      ctl: Optional["GradCtl"] = None, n: Optional[torch.Tensor] = None) -> None:
         """``scone_opt_step_lean``: the lean optimizer step (include/scone_hip.h, "lean optimizer step").  ``kind``: ``"sgd"`` or
         ``"rowwise_adagrad"`` (ONE fp32 accumulator per row: ``row_state``, fp32 ``[row_end - row_begin]``, contiguous, on the
         table's device, updated in place).  ``master`` given (fp32 ``[row_end - row_begin, d]``): it is updated in place and
         the served rows are re-stored in the table's format, as :meth:`opt_step` does.  ``master=None``: IN PLACE -- the served
         fp32 / bf16 rows are the weights; bf16 rows are rounded to ``"nearest"`` or ``"stochastic"`` (random bits keyed by
         ``seed``, ``step``, the global row id and the column).  One kernel launch on the current stream; no synchronisation.
-        ``ctl`` (a :class:`GradCtl`): ``scone_opt_step_lean_ctl``, as for :meth:`opt_step`."""
+        ``ctl`` (a :class:`GradCtl`): ``scone_opt_step_lean_ctl``, as for :meth:`opt_step`.  ``n`` (a 1-element int64 device
+        tensor): ``scone_opt_step_lean_dn``, as for :meth:`opt_step`; under capture a replay repeats the stochastic rounding's
+        ``step`` as captured."""
         cfg = _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step)
         owned = self.row_end - self.row_begin
         if master is None and self.fmt not in (L.FMT_F32, L.FMT_BF16):
@@ -1348,6 +1542,14 @@ class SconeTable:
             raise ValueError("opt_step_lean: row_ids must be int64 and grad_rows fp32")
         row_ids = row_ids.to(device=self.device).contiguous()
         grad_rows = grad_rows.to(device=self.device).contiguous()
+        if n is not None:
+            n = _device_count("opt_step_lean", n, self.device)
+            with torch.cuda.device(self.device):
+                rc = L.lib().scone_opt_step_lean_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
+                                                    _ptr(master), _ptr(row_state), None if ctl is None else _ptr(ctl.buf),
+                                                    torch.cuda.current_stream(self.device).cuda_stream)
+            self._check(rc, "scone_opt_step_lean_dn")
+            return
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             if ctl is None:

@@ -61,6 +61,42 @@ def _library_operand(grad: Optional[torch.Tensor], table):
     return grad._indices()[0], grad._values()
 
 
+class _StaticGrad:
+    """The buffers of a module in static mode (``static_rows=``): one :class:`~scone_amd.hip_backend.BackwardContext` and one
+    ``(ids [cap] int64, rows [cap, d] fp32, n [1] int64)`` set, allocated once.  The backward fills them with the count left on
+    the device, so ``forward; backward; FGramOptimizer.step()`` neither synchronises nor allocates and can be captured in a
+    ``torch.cuda.graph`` and replayed on new tokens (include/scone_hip.h, "backward and optimizer step without a host
+    synchronisation")."""
+
+    def __init__(self, table, static_rows: int, max_tokens: int) -> None:
+        if max_tokens is None or int(max_tokens) <= 0:
+            raise ValueError("static_rows= needs max_tokens=: the most positions a batch can have")
+        if int(static_rows) <= 0:
+            raise ValueError("static_rows must be positive: the most distinct rows a batch can touch")
+        self.cap = int(static_rows)
+        self.ctx = table.backward_context(int(max_tokens))
+        self.ids = torch.zeros(self.cap, dtype=torch.int64, device=table.device)
+        self.rows = torch.zeros((self.cap, table.dim), dtype=torch.float32, device=table.device)
+        self.n = torch.zeros(1, dtype=torch.int64, device=table.device)
+
+    def check(self, module, ctx_base_dtype) -> None:
+        """The refusals of a static backward: ``ValueError`` before any device work."""
+        if getattr(module, "_fused_opt", None) is not None:
+            raise ValueError("static_rows= and fused_backward=True do not go together (scone_backward_apply_lean takes a plan "
+                             "whose counts are on the host)")
+        if module.static_grad is not None:
+            raise ValueError("static_rows=: a gradient is already there, and accumulation over micro-batches is not available "
+                             "with the counts on the device; call zero_grad() between backwards, or build the module without "
+                             "static_rows=")
+        if ctx_base_dtype is not None and module.cache.lookup_mode == "longest_suffix":
+            raise ValueError("static_rows= with base= on a longest_suffix cache is not available (grad_base needs the hit counts "
+                             "of a plan)")
+
+    def backward(self, module, tok, cu, grad_out, reduce) -> None:
+        self.ctx.plan(tok, cu)
+        module.static_grad = self.ctx.rows(grad_out, reduce, out=(self.ids, self.rows, self.n))
+
+
 class _Lookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, base, module, input_ids, cu_seqlens, reduce, out_dtype):
@@ -86,6 +122,14 @@ class _Lookup(torch.autograd.Function):
         table = module.cache.to_device()
         grad_weight = grad_base = None
         grad_out = grad_out.contiguous()
+        static = getattr(module, "_static", None)
+        if static is not None:                                # static_rows=: the counts stay on the device
+            static.check(module, ctx.base_dtype)
+            if ctx.needs_input_grad[0]:
+                static.backward(module, ctx.tok, ctx.cu, grad_out, ctx.reduce)
+            if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
+                grad_base = grad_out.to(ctx.base_dtype).reshape(ctx.base_shape)
+            return grad_weight, grad_base, None, None, None, None, None
         fused = getattr(module, "_fused_opt", None)           # an FGramOptimizer(fused_backward=True): the update happens here
         with table.backward_plan(ctx.tok, ctx.cu) as plan:
             if ctx.needs_input_grad[0] and fused is not None:
@@ -126,9 +170,16 @@ class TrainableFGramTable(nn.Module):
     (cover mode) or ``grad_out * (K == 0)`` (longest suffix: a matched f-gram replaced the base row).
     :meth:`commit` re-stores the rows touched since the last commit into the served table, after which it equals a table built
     from the updated weights.  The cache's host copy of the rows, if it keeps one, is not updated: it is the table at
-    ingestion time."""
+    ingestion time.
 
-    def __init__(self, cache: EmbeddingCache, weight: torch.Tensor) -> None:
+    ``static_rows=cap, max_tokens=`` (static mode; :class:`FGramOptimizer` only): the backward plans in one
+    ``BackwardContext`` of ``max_tokens`` positions and writes into one ``(ids [cap], rows [cap, d], n)`` buffer set, with the
+    row count ``n`` left on the device, and sets ``static_grad`` to that triple instead of ``weight.grad``; nothing
+    synchronises or allocates, so ``forward; backward; opt.step()`` can be captured and replayed.  A batch that touches more
+    than ``cap`` rows writes nothing and the step changes nothing (``opt.rows_overflowed()``)."""
+
+    def __init__(self, cache: EmbeddingCache, weight: torch.Tensor, static_rows: Optional[int] = None,
+                 max_tokens: Optional[int] = None) -> None:
         super().__init__()
         table = cache.to_device()
         if not isinstance(weight, nn.Parameter):
@@ -138,6 +189,8 @@ class TrainableFGramTable(nn.Module):
         self.cache = cache
         self.weight = weight
         self._touched = []
+        self._static = None if static_rows is None else _StaticGrad(table, static_rows, max_tokens)
+        self.static_grad = None         # static mode: (ids, rows, n) after a backward
 
     def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
                 out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -183,9 +236,11 @@ class InPlaceFGramTable(nn.Module):
     :class:`TrainableFGramTable`'s.  ``anchor``, a parameter of zero elements, only makes autograd call the backward; the
     sparse gradient lands on the module as ``grad = (row_ids, grad_rows)`` -- ``row_ids`` int64 ``[U]`` sorted and distinct,
     ``grad_rows`` fp32 ``[U, d]`` -- and a backward onto a gradient that is already there adds to it (a row both have is one fp32
-    add, a row one has is that row, bit for bit).  Only :class:`FGramOptimizer` (``"sgd"`` or ``"rowwise_adagrad"``) updates it."""
+    add, a row one has is that row, bit for bit).  Only :class:`FGramOptimizer` (``"sgd"`` or ``"rowwise_adagrad"``) updates it.
+    ``static_rows=cap, max_tokens=``: static mode, as on :class:`TrainableFGramTable` -- the backward sets ``static_grad =
+    (ids, rows, n)`` with the count on the device, and ``grad`` stays ``None``."""
 
-    def __init__(self, cache: EmbeddingCache) -> None:
+    def __init__(self, cache: EmbeddingCache, static_rows: Optional[int] = None, max_tokens: Optional[int] = None) -> None:
         super().__init__()
         table = cache.to_device()
         self.cache = cache
@@ -193,6 +248,8 @@ class InPlaceFGramTable(nn.Module):
         self.anchor = nn.Parameter(torch.zeros(0, dtype=torch.float32, device=table.device))
         self.grad = None
         self._fused_opt = None          # set by FGramOptimizer(fused_backward=True)
+        self._static = None if static_rows is None else _StaticGrad(table, static_rows, max_tokens)
+        self.static_grad = None         # static mode: (ids, rows, n) after a backward
 
     def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
                 out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -276,10 +333,14 @@ class FGramOptimizer:
         self.state1: Optional[torch.Tensor] = None     # Adam's m
         self.state2: Optional[torch.Tensor] = None     # Adam's v / Adagrad's sum of squares
         self.last_ctl = None                           # the GradCtl of the last clipped / guarded step()
+        self._static_ctl = self._static_sq = self._static_scratch = None    # static mode: kept across steps (and replays)
 
     def _set_fused(self, on: bool) -> None:
         on = bool(on)
         if on:
+            if getattr(self.module, "_static", None) is not None:
+                raise ValueError("fused_backward=True and a module built with static_rows= do not go together "
+                                 "(scone_backward_apply_lean takes a plan whose counts are on the host)")
             if not self.in_place:
                 raise ValueError("fused_backward is for an InPlaceFGramTable: a TrainableFGramTable's master rows are updated by "
                                  "step()")
@@ -339,10 +400,77 @@ class FGramOptimizer:
         0-dim float64 tensor on the table's device, summed in the fixed order of ``scone_grad_sqnorm``: the same bits on every
         run.  No gradient: zero.  No synchronisation."""
         table = self.module.cache.to_device()
+        static = getattr(self.module, "static_grad", None)
+        if static is not None:
+            return table.grad_sqnorm(static[1], n=static[2])[0]
         grad = self._current_grad()
         if grad is None:
             return torch.zeros((), dtype=torch.float64, device=table.device)
         return table.grad_sqnorm(grad[1])[0]
+
+    def rows_overflowed(self) -> bool:
+        """Static mode: whether a backward since the last call touched more rows than ``static_rows`` -- it then wrote nothing,
+        left ``n = 0``, and the step behind it changed nothing.  Reads and CLEARS the table's sticky status bits (all of them,
+        as ``table.status()`` does).  SYNCHRONISES."""
+        return self.module.cache.to_device().rows_overflowed()
+
+    def _static_state_ready(self) -> bool:
+        if self.kind == "rowwise_adagrad":
+            return self.state2 is not None
+        if self.in_place:
+            return True
+        return (self.kind != "adam" or self.state1 is not None) and (self.kind == "sgd" or self.state2 is not None)
+
+    def _step_static(self, static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite) -> int:
+        """``step()`` on the triple of a static backward: the ``_dn`` calls, which read the row count on the device."""
+        ids, rows, n = static
+        module = self.module
+        table = module.cache.to_device()
+        if torch.cuda.is_current_stream_capturing():
+            # the step-dependent scalars are launch arguments: a replayed graph would repeat them as captured
+            if self.kind == "adam":
+                raise ValueError("FGramOptimizer.step under capture: Adam's bias correction depends on the step count, which a "
+                                 "replayed graph would repeat as captured; use sgd, adagrad or rowwise_adagrad, or step eagerly")
+            if self.rounding == "stochastic":
+                raise ValueError("FGramOptimizer.step under capture: stochastic rounding draws its bits from the step count, which "
+                                 "a replayed graph would repeat as captured; use rounding='nearest', or step eagerly")
+            if not self._static_state_ready() or (ctl_road and self._static_ctl is None):
+                raise ValueError("FGramOptimizer.step under capture: the optimizer state is allocated at the first step; run one "
+                                 "step eagerly (the warm-up) before capturing")
+        lo, hi = table.row_begin, table.row_end
+        ctl = None
+        if ctl_road:
+            if self._static_ctl is None:
+                from scone_amd.hip_backend import GradCtl
+                self._static_ctl = GradCtl(table.device)
+                self._static_sq = torch.zeros((), dtype=torch.float64, device=table.device)
+                self._static_scratch = torch.zeros(_lib.grad_sqnorm_scratch(rows.shape[0]), dtype=torch.float64, device=table.device)
+            extra = [] if extra_sqnorm is None else (list(extra_sqnorm) if isinstance(extra_sqnorm, (list, tuple)) else [extra_sqnorm])
+            sq = table.grad_sqnorm(rows, self._static_scratch, n=n, out=self._static_sq)[0]
+            ctl = table.grad_ctl([sq, *extra], grad_scale=grad_scale, max_norm=max_norm, skip_nonfinite=skip_nonfinite,
+                                 out=self._static_ctl)
+            self.last_ctl = ctl
+        self.t += 1
+        self._ensure_state()
+
+        def own(x):
+            return None if x is None else x[lo:hi]
+
+        if self.in_place:
+            table.opt_step_lean(ids, rows, kind=self.kind, lr=self.lr, row_state=own(self.state2), eps=self.eps,
+                                weight_decay=self.weight_decay, grad_scale=grad_scale, rounding=self.rounding, seed=self.seed,
+                                step=self.t, ctl=ctl, n=n)
+        elif self.kind == "rowwise_adagrad":
+            table.opt_step_lean(ids, rows, kind=self.kind, lr=self.lr, master=own(module.weight.detach()),
+                                row_state=own(self.state2), eps=self.eps, weight_decay=self.weight_decay, grad_scale=grad_scale,
+                                step=self.t, ctl=ctl, n=n)
+        else:
+            table.opt_step(ids, rows, own(module.weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
+                           state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                           grad_scale=grad_scale, ctl=ctl, n=n)
+        if not self.in_place:
+            module._touched = []                         # the served table is current: commit() has nothing to store
+        return int(ids.numel())
 
     def found_nonfinite(self) -> bool:
         """Whether the last ``step(...)`` that took a clipping / skipping argument found inf or NaN and skipped (with
@@ -365,8 +493,19 @@ class FGramOptimizer:
         ``skip_nonfinite=True`` skips the step if any term is inf or NaN.  ``t`` ADVANCES ON A DEVICE-SKIPPED STEP TOO: the
         host does not know the outcome.  A caller who wants Adam's ``t`` unchanged by a skipped step calls
         :meth:`found_nonfinite` (a synchronise) and sets ``opt.t -= 1``.  With none of the three set, the step is the plain
-        one."""
+        one.
+
+        Static mode (a module built with ``static_rows=``): the gradient is ``module.static_grad``, whose row count is on the
+        device; the ``_dn`` calls read it there, the norm's scratch and the control block are kept on the optimizer, and nothing
+        synchronises or allocates after the first step -- the step can be captured.  Returns the buffers' capacity (the count
+        itself is ``module.static_grad[2]``).  While the stream is capturing, ``kind="adam"`` and ``rounding="stochastic"`` are
+        refused (``ValueError``): their step-dependent scalars are launch arguments, which a replay repeats as captured.
+        Eagerly both work.  A backward that overflowed ``static_rows`` left ``n = 0``: the step changes nothing
+        (:meth:`rows_overflowed`)."""
         ctl_road = max_norm is not None or extra_sqnorm is not None or bool(skip_nonfinite)
+        static = getattr(self.module, "static_grad", None)
+        if static is not None:
+            return self._step_static(static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite)
         if self.fused_backward:
             if ctl_road:
                 raise ValueError("FGramOptimizer.step: max_norm / extra_sqnorm / skip_nonfinite need the gradient's norm before the "
@@ -416,6 +555,8 @@ class FGramOptimizer:
         return int(row_ids.numel())
 
     def zero_grad(self, set_to_none: bool = True) -> None:
+        if getattr(self.module, "_static", None) is not None:
+            self.module.static_grad = None               # the buffers stay; the next backward fills them again
         if self.in_place:
             module = self.module
             if module.grad is not None and not set_to_none:
