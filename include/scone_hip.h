@@ -987,6 +987,89 @@ int scone_backward_rows_acc(scone_handle *h, scone_bwd_plan *plan, const void *d
                             const uint32_t *d_src_old, const uint32_t *d_src_new, const uint32_t *d_pos_new, uint64_t n_out,
                             const float *d_rows_old, float *d_rows_out, scone_stream_t stream);
 
+/* ---- optimizer hyper-parameters on the device: a captured step with Adam, stochastic rounding, a learning-rate schedule and a
+ * dynamic loss scale (new here; torch.optim.Adam(capturable=True) keeps its step count on the device for the same reason).
+ * SCONE_ABI_VERSION is unchanged; every other entry point keeps its bits, its refusals and its stream contract.  The section
+ * stands IN FRONT of the one it builds on ("backward and optimizer step without a host synchronisation", next): the header ends
+ * with scone_embed_select, and that section's prototypes are counted; a declaration's place changes nothing for a compiler.
+ * What it is for: the by-value steps take lr, grad_scale, Adam's t and the stochastic rounding's step BY VALUE, so a replayed graph
+ * repeats them as captured, and the host counts a step that the device skipped.  Here they live in a block of 104 bytes on the
+ * device (8-byte aligned): scone_opt_hyper_init writes it, scone_opt_hyper_advance counts the step and derives the fp32 scalars
+ * ON THE DEVICE, and scone_opt_step_dh / scone_opt_step_lean_dh / scone_grad_ctl_set_dh read them there.  Between steps the
+ * caller may overwrite any input field with stream-ordered device work of its own (a copy, a fill, a scheduler kernel).
+ * No call of this section synchronises or allocates; all are stream-ordered.
+ *
+ * 1. Scalars.  scone_opt_hyper_scalars_of(cfg, out) is the host copy of what the advance derives at t = cfg->step (no GPU, no
+ *   handle, as scone_lean_rand16): a PURE FUNCTION of (cfg, t).  It equals scone_opt_scalars_of in every field but Adam's
+ *   alpha, which uses a stated integer power instead of libm's pow, so that host and device agree bit for bit:
+ *     ipow(b, t):  r = 1.0; while (t) { if (t & 1) r = r * b; t >>= 1; if (t) b = b * b; }     (every product ONE IEEE double)
+ *     alpha = (float)((lr * sqrt(1 - ipow(beta2, t))) / (1 - ipow(beta1, t)))                    (ADAM; sqrt and / correctly
+ *             rounded in double, as scone_grad_ctl_set relies on; SGD, ADAGRAD: alpha = (float)lr)
+ *   It can differ from scone_opt_scalars_of's alpha by at most one fp32 ulp (the two powers differ by a few double ulps, far
+ *   below half an fp32 ulp except at a rounding boundary); for lr = 1e-3, betas (0.9, 0.999), (0.9, 0.95), (0.5, 0.99),
+ *   (0.0, 0.999) and t = 1 .. 20000, 10^6, 12345678, 2^31 - 1 the two were identical.  Refusals: scone_opt_scalars_of's.
+ *
+ * 2. scone_opt_hyper_init(h, cfg, seed, d_hyper): ONE launch of one thread stores the six doubles of cfg (taken by value),
+ *   seed, step = cfg->step -- here the number of steps ALREADY APPLIED, so >= 0 (0 for a fresh optimizer) -- and sc = 0,
+ *   applied = 0, bad = 0.  cfg->kind is only checked: the block holds no kind.  SCONE_EINVAL (prefixed
+ *   "scone_opt_hyper_init: "): what scone_opt_step refuses of a cfg, with step < 0 (any kind) in place of step < 1; a null d_hyper.
+ *
+ * 3. scone_opt_hyper_advance(h, kind, d_hyper, d_ctl): ONE launch of one thread, once per optimizer step, before the step
+ *   kernels.  kind is SCONE_OPT_*; the lean steps advance with SCONE_OPT_SGD (alpha = lr).  d_ctl may be NULL.
+ *     d_ctl != NULL and d_ctl->skip != 0:   applied = 0; NOTHING else changes, step included
+ *     else, any of the six doubles is inf or NaN, or step == INT64_MAX:   applied = 0, bad = 1; nothing else changes
+ *     else:   step = step + 1; sc = scone_opt_hyper_scalars_of's values at the new step; applied = 1; bad = 0
+ *   So step counts the steps APPLIED: a step the device skipped does not advance Adam's t or the stochastic bits.  All stores
+ *   are plain stores of thread 0.  SCONE_EINVAL: a bad kind, a null d_hyper.
+ *
+ * 4. scone_opt_step_dh / scone_opt_step_lean_dh: scone_opt_step_dn / scone_opt_step_lean_dn (next section) with the scalars
+ *   read from d_hyper->sc, and for SCONE_ROUND_STOCHASTIC the random bits' seed and step read from d_hyper->seed / d_hyper->step (the
+ *   step the advance left: the number of this step).  kind (and rounding) come by value; d_n is required -- a caller who knows n
+ *   on the host passes a device word that holds it.  Every wavefront first reads `applied`: if it is 0, or d_ctl != NULL and
+ *   d_ctl->skip is set, the launch changes NOTHING -- no row, no state, no scale, no status bit.  Otherwise, with d_ctl,
+ *   gscale_eff = sc.gscale * coef is ONE fp32 product, as in the _ctl steps.  Contract: every bit of master, state, table and
+ *   scales equals scone_opt_step_dn / scone_opt_step_lean_dn given those scalars (and that seed and step): the same kernels,
+ *   instantiated for scalars on the device; the block's fields are loaded once per wavefront, before its first row.
+ *   ONE launch, no synchronisation, no allocation; n_cap == 0: a no-op.  SCONE_EINVAL: the refusals of the _dn calls that the
+ *   host can still check (handle, table, kind, rounding, modes and formats, null pointers and state arrays, a null d_n), plus a
+ *   null d_hyper.  What the host can no longer check -- a value that is not finite -- is the advance's `bad`.
+ *
+ * 5. scone_grad_ctl_set_dh: scone_grad_ctl_set with grad_scale read from d_hyper->grad_scale; the arithmetic and the bits are
+ *   the same.  A grad_scale that is inf or NaN on the device gives skip = 1 and coef = 1.0f (the by-value call refuses such a
+ *   value; on the device the call can only decline to step).  One launch.  SCONE_EINVAL: as scone_grad_ctl_set, plus a null
+ *   d_hyper.
+ *
+ * Order of a guarded step: scone_grad_sqnorm_dn, scone_grad_ctl_set_dh, scone_opt_hyper_advance(d_ctl), then
+ * scone_opt_step_dh / scone_opt_step_lean_dh(d_ctl).  One block may serve several tables or shards: advance ONCE, step each
+ * (with steps of the kind the advance was given; SGD and the lean steps share alpha = lr).
+ *
+ * The stream.  As in the next section: every call that enqueues work takes `stream` last, a hipStream_t passed as void *.
+ *
+ * Left out, and meant to be: scone_backward_apply_lean in this form, and accumulation in _dn form (see the next section). */
+typedef struct scone_opt_hyper {
+  /* inputs: written by scone_opt_hyper_init; between steps the caller may overwrite any of them with stream-ordered device
+     work of their own (a copy, a fill, a scheduler kernel) */
+  double lr, beta1, beta2, eps, weight_decay, grad_scale; /* 0 .. 48 */
+  uint64_t seed;                                          /* 48: stochastic rounding only */
+  int64_t step;                                           /* 56: t = steps APPLIED so far */
+  /* derived by scone_opt_hyper_advance */
+  scone_opt_scalars sc;                                   /* 64: the 8 floats the step kernels use */
+  uint32_t applied;                                       /* 96: 1 = the last advance advanced */
+  uint32_t bad;                                           /* 100: 1 = the last advance found a non-finite input */
+} scone_opt_hyper;                                        /* 104 bytes */
+int scone_opt_hyper_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars *out);
+int scone_opt_hyper_init(scone_handle *h, const scone_opt_cfg *cfg, uint64_t seed, scone_opt_hyper *d_hyper, void *stream);
+int scone_opt_hyper_advance(scone_handle *h, int32_t kind, scone_opt_hyper *d_hyper, const scone_grad_ctl *d_ctl /* may be NULL */,
+                            void *stream);
+int scone_opt_step_dh(scone_handle *h, int32_t kind, const int64_t *d_row_ids, const float *d_grad_rows, const uint64_t *d_n,
+                      uint64_t n_cap, float *d_master, float *d_state1, float *d_state2, const scone_opt_hyper *d_hyper,
+                      const scone_grad_ctl *d_ctl, void *stream);
+int scone_opt_step_lean_dh(scone_handle *h, int32_t kind, int32_t rounding, const int64_t *d_row_ids, const float *d_grad_rows,
+                           const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_row_state,
+                           const scone_opt_hyper *d_hyper, const scone_grad_ctl *d_ctl, void *stream);
+int scone_grad_ctl_set_dh(scone_handle *h, const double *d_terms, int32_t n_terms, const scone_opt_hyper *d_hyper, double max_norm,
+                          int32_t skip_nonfinite, scone_grad_ctl *d_ctl, void *stream);
+
 /* ---- backward and optimizer step without a host synchronisation: a step that can be captured (new here; appended,
  * SCONE_ABI_VERSION unchanged; every entry point above keeps its bits, its refusals and its place in the stream contract).
  * What it is for: scone_backward_plan reads its counts back (one synchronisation), allocates the partial slots from them and
@@ -1061,9 +1144,11 @@ int scone_backward_rows_acc(scone_handle *h, scone_bwd_plan *plan, const void *d
  * The stream.  Every call of this section that enqueues work takes `stream` last: a hipStream_t passed as void * (what
  * scone_stream_t is; NULL = the default stream), the stream all of its device work is enqueued on.
  *
- * Scalars under capture.  The steps still take their hyper-parameters by value (scone_opt_scalars_of / scone_lean_scalars_of
- * run on the host): Adam's step t inside alpha and the stochastic rounding's `step` are part of a captured launch and a
- * replayed graph repeats them AS CAPTURED.  SGD, Adagrad, row-wise Adagrad and round-to-nearest have no such scalar.
+ * Scalars under capture.  The steps of THIS section take their hyper-parameters by value (scone_opt_scalars_of /
+ * scone_lean_scalars_of run on the host): lr, grad_scale, Adam's step t inside alpha and the stochastic rounding's `step` are
+ * part of a captured launch and a replayed graph repeats them AS CAPTURED.  The section "optimizer hyper-parameters on the
+ * device" in front of this one keeps them in a block on the device instead: scone_opt_step_dh / scone_opt_step_lean_dh are
+ * the steps of this section with the scalars read there, and every kind and rounding can be captured.
  *
  * Left out, and meant to be: scone_backward_apply_lean in this form (the fused backward + lean step still takes a
  * scone_bwd_plan), and accumulation (scone_backward_rows_acc, scone_grad_merge_*) in this form -- a step that accumulates over

@@ -100,6 +100,24 @@ class SconeGradCtl(C.Structure):
     ]
 
 
+class SconeOptHyper(C.Structure):
+    """``scone_opt_hyper``: the 104 device bytes ``scone_opt_hyper_init`` writes, ``scone_opt_hyper_advance`` advances and the
+    ``_dh`` steps read (include/scone_hip.h, "optimizer hyper-parameters on the device")."""
+    _fields_ = [
+        ("lr", C.c_double),
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("eps", C.c_double),
+        ("weight_decay", C.c_double),
+        ("grad_scale", C.c_double),
+        ("seed", C.c_uint64),
+        ("step", C.c_int64),
+        ("sc", OptScalars),
+        ("applied", C.c_uint32),
+        ("bad", C.c_uint32),
+    ]
+
+
 _P = C.c_void_p
 _I32, _I64, _U32, _U64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 
@@ -252,6 +270,12 @@ SIGNATURES = {
     "scone_opt_step_dn": (C.c_int, [_P, C.POINTER(OptCfg), _P, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "scone_opt_step_lean_dn": (C.c_int, [_P, C.POINTER(LeanCfg), _P, _P, _P, _U64, _P, _P, _P, _P]),
     "scone_grad_sqnorm_dn": (C.c_int, [_P, _P, _P, _U64, _P, _P, _P]),
+    "scone_opt_hyper_scalars_of": (C.c_int, [C.POINTER(OptCfg), C.POINTER(OptScalars)]),
+    "scone_opt_hyper_init": (C.c_int, [_P, C.POINTER(OptCfg), _U64, _P, _P]),
+    "scone_opt_hyper_advance": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "scone_opt_step_dh": (C.c_int, [_P, _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "scone_opt_step_lean_dh": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "scone_grad_ctl_set_dh": (C.c_int, [_P, _P, _I32, _P, C.c_double, _I32, _P, _P]),
 }
 
 _lock = threading.Lock()

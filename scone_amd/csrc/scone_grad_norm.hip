@@ -97,10 +97,27 @@ __global__ __launch_bounds__(GN_THREADS) void k_grad_total_sq(const double *__re
   if (threadIdx.x == 0) *out = sum;
 }
 
+// where k_grad_ctl_set takes grad_scale from: the launch (checked finite on the host), or the scone_opt_hyper block of
+// scone_grad_ctl_set_dh, where a value that is not finite can only be answered on the device
+struct gn_scale_value {
+  double v;
+  __device__ __forceinline__ double get() const { return v; }
+  __device__ __forceinline__ bool finite(double) const { return true; }
+};
+struct gn_scale_device {
+  const scone_opt_hyper *__restrict__ hy;
+  __device__ __forceinline__ double get() const { return hy->grad_scale; }
+  __device__ __forceinline__ bool finite(double x) const {
+    return ((unsigned long long)__double_as_longlong(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+  }
+};
+
 // one thread, every operation one IEEE double rounding; sqrt and / are hipcc's correctly rounded defaults
-__global__ void k_grad_ctl_set(const double *__restrict__ terms, int n_terms, double grad_scale, double max_norm, int skip_nonfinite,
+template <typename GSRC>
+__global__ void k_grad_ctl_set(const double *__restrict__ terms, int n_terms, GSRC gsrc, double max_norm, int skip_nonfinite,
                                scone_grad_ctl *__restrict__ ctl) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double grad_scale = gsrc.get();
   double total = 0.0;
   for (int i = 0; i < n_terms; ++i) total = total + terms[i];
   const double norm64 = sqrt(total) * fabs(grad_scale);
@@ -111,6 +128,10 @@ __global__ void k_grad_ctl_set(const double *__restrict__ terms, int n_terms, do
   ctl->coef = c < 1.0 ? (float)c : 1.0f;  // a NaN compares false: 1.0f
   ctl->skip = skip_nonfinite && !finite ? 1u : 0u;
   ctl->reserved = 0u;
+  if (!gsrc.finite(grad_scale)) {  // scone_grad_ctl_set_dh only: the by-value call has refused such a scale on the host
+    ctl->coef = 1.0f;
+    ctl->skip = 1u;
+  }
 }
 
 unsigned long long gn_tiles(unsigned long long n) { return n / GN_TILE + (n % GN_TILE ? 1 : 0); }
@@ -181,8 +202,23 @@ extern "C" int scone_grad_ctl_set(scone_handle *h, const double *d_terms, int32_
   if (!std::isfinite(grad_scale)) return scone_refuse(h, SCONE_EINVAL, who, "grad_scale must be finite");
   if (!(max_norm > 0.0)) return scone_refuse(h, SCONE_EINVAL, who, "max_norm must be > 0 (+inf: no clipping)");
   SCONE_ON_DEVICE(h);
-  hipLaunchKernelGGL(k_grad_ctl_set, dim3(1), dim3(1), 0, (hipStream_t)stream, d_terms, (int)n_terms, grad_scale, max_norm,
-                     (int)skip_nonfinite, d_ctl);
+  hipLaunchKernelGGL(k_grad_ctl_set<gn_scale_value>, dim3(1), dim3(1), 0, (hipStream_t)stream, d_terms, (int)n_terms,
+                     gn_scale_value{grad_scale}, max_norm, (int)skip_nonfinite, d_ctl);
+  SCONE_HIP(h, hipGetLastError());
+  return SCONE_OK;
+}
+
+extern "C" int scone_grad_ctl_set_dh(scone_handle *h, const double *d_terms, int32_t n_terms, const scone_opt_hyper *d_hyper,
+                                     double max_norm, int32_t skip_nonfinite, scone_grad_ctl *d_ctl, void *stream) {
+  const char *who = "scone_grad_ctl_set_dh";
+  if (!h) return SCONE_EINVAL;
+  if (n_terms < 1 || n_terms > 64) return scone_refuse(h, SCONE_EINVAL, who, "n_terms must be 1 .. 64");
+  if (!d_terms || !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
+  if (!d_hyper) return scone_refuse(h, SCONE_EINVAL, who, "null d_hyper");
+  if (!(max_norm > 0.0)) return scone_refuse(h, SCONE_EINVAL, who, "max_norm must be > 0 (+inf: no clipping)");
+  SCONE_ON_DEVICE(h);
+  hipLaunchKernelGGL(k_grad_ctl_set<gn_scale_device>, dim3(1), dim3(1), 0, (hipStream_t)stream, d_terms, (int)n_terms,
+                     gn_scale_device{d_hyper}, max_norm, (int)skip_nonfinite, d_ctl);
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
 }

@@ -53,13 +53,16 @@ __device__ __forceinline__ void opt_elem(const scone_opt_scalars &k, float g, fl
 }
 
 // One wave per listed row; the grid-stride loop over rows is k_store_f32's.  NSRC (scone_opt_rows.h): n by value, or the count
-// scone_opt_step_dn reads from the device.
-template <int FMT, int KIND, typename NSRC>
+// scone_opt_step_dn reads from the device.  SSRC (scone_opt_rows.h): the scalars by value, or the scone_opt_hyper block
+// scone_opt_step_dh reads them from -- a block whose last advance did not apply ends the wave before it touches anything.
+template <int FMT, int KIND, typename NSRC, typename SSRC>
 __global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ ids, const float *__restrict__ grad,
                                                   NSRC nsrc, unsigned long long row_begin, unsigned long long row_end,
-                                                  int d, scone_opt_scalars sc, float *__restrict__ master, float *__restrict__ state1,
+                                                  int d, SSRC ssrc, float *__restrict__ master, float *__restrict__ state1,
                                                   float *__restrict__ state2, scone_row_store st, __half *__restrict__ scales,
                                                   uint32_t *__restrict__ status, const scone_grad_ctl *__restrict__ ctl) {
+  scone_opt_scalars sc;
+  if (!ssrc.load(sc)) return;
   // scone_opt_step_ctl (ctl != null; wave-uniform): a set skip flag ends the wave before it touches anything; else the block's
   // coef joins gscale by one fp32 product and the rest is the plain call with that gscale
   if (ctl) {
@@ -127,17 +130,6 @@ __global__ __launch_bounds__(256) void k_opt_step(const int64_t *__restrict__ id
   }
 }
 
-const char *opt_check(const scone_opt_cfg *cfg) {
-  if (!cfg) return "null cfg";
-  if (cfg->struct_size != sizeof(scone_opt_cfg)) return "cfg.struct_size does not match this library";
-  if (cfg->kind != SCONE_OPT_SGD && cfg->kind != SCONE_OPT_ADAGRAD && cfg->kind != SCONE_OPT_ADAM) return "bad kind";
-  if (!std::isfinite(cfg->lr) || !std::isfinite(cfg->beta1) || !std::isfinite(cfg->beta2) || !std::isfinite(cfg->eps) ||
-      !std::isfinite(cfg->weight_decay) || !std::isfinite(cfg->grad_scale))
-    return "lr, beta1, beta2, eps, weight_decay and grad_scale must be finite";
-  if (cfg->kind == SCONE_OPT_ADAM && cfg->step < 1) return "Adam needs step >= 1";
-  return nullptr;
-}
-
 void opt_scalars(const scone_opt_cfg *cfg, scone_opt_scalars *out) {
   double alpha = cfg->lr;
   if (cfg->kind == SCONE_OPT_ADAM) {
@@ -162,18 +154,23 @@ struct opt_args {
   float *master, *s1, *s2;
   const scone_grad_ctl *ctl;  // null: scone_opt_step
   const unsigned long long *d_n;  // scone_opt_step_dn: the count on the device, n its cap; null: n by value
+  const scone_opt_hyper *hyper;   // scone_opt_step_dh: the scalars on the device (d_n is set too); null: sc by value
 };
 
 template <int FMT, int KIND>
 void opt_launch(scone_handle *h, const opt_args &a, unsigned blocks, hipStream_t s) {
-  if (a.d_n)
-    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_device>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, opt_n_device{a.d_n, a.n},
-                       (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2,
-                       scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
+  if (a.hyper)
+    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_device, opt_s_device>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
+                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
+                       opt_s_device{a.hyper}, a.master, a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
+  else if (a.d_n)
+    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_device, opt_s_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
+                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
+                       opt_s_value{a.sc}, a.master, a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
   else
-    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, opt_n_value{a.n},
-                       (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, a.sc, a.master, a.s1, a.s2,
-                       scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
+    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_value, opt_s_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, opt_n_value{a.n},
+                       (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, opt_s_value{a.sc}, a.master,
+                       a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
 }
 
 template <int FMT>
@@ -189,31 +186,39 @@ void opt_launch_kind(scone_handle *h, int kind, const opt_args &a, unsigned bloc
 }  // namespace
 
 extern "C" int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars *out) {
-  if (!out || opt_check(cfg)) return SCONE_EINVAL;
+  if (!out || opt_cfg_check(cfg)) return SCONE_EINVAL;
   opt_scalars(cfg, out);
   return SCONE_OK;
 }
 
 namespace {
 
-// scone_opt_step (with_ctl false, ctl null), scone_opt_step_ctl and scone_opt_step_dn (with_n: n is the cap of *d_n)
+// scone_opt_step (with_ctl false, ctl null), scone_opt_step_ctl, scone_opt_step_dn (with_n: n is the cap of *d_n) and
+// scone_opt_step_dh (with_hyper: cfg is null, the kind comes by value and the scalars from *d_hyper)
 int opt_step(scone_handle *h, const char *who, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
              float *d_master, float *d_state1, float *d_state2, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream,
-             bool with_n = false, const uint64_t *d_n = nullptr) {
-  SCONE_TRY(opt_need_table(h, who, opt_check(cfg)));
+             bool with_n = false, const uint64_t *d_n = nullptr, bool with_hyper = false, int32_t kind_dh = 0,
+             const scone_opt_hyper *d_hyper = nullptr) {
+  const int kind = with_hyper ? kind_dh : cfg ? cfg->kind : 0;
+  const char *bad_cfg = !with_hyper ? opt_cfg_check(cfg)
+                        : kind != SCONE_OPT_SGD && kind != SCONE_OPT_ADAGRAD && kind != SCONE_OPT_ADAM ? "bad kind" : nullptr;
+  SCONE_TRY(opt_need_table(h, who, bad_cfg));
   if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
   if (with_n && !d_n) return scone_refuse(h, SCONE_EINVAL, who, "null d_n");
+  if (with_hyper && !d_hyper) return scone_refuse(h, SCONE_EINVAL, who, "null d_hyper");
   if (n == 0) return SCONE_OK;
   if (!d_row_ids || !d_grad_rows || !d_master) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
-  if (cfg->kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, who, "Adam needs d_state1 (m)");
-  if (cfg->kind != SCONE_OPT_SGD && !d_state2) return scone_refuse(h, SCONE_EINVAL, who, "Adam / Adagrad need d_state2 (v / the sum of squares)");
+  if (kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, who, "Adam needs d_state1 (m)");
+  if (kind != SCONE_OPT_SGD && !d_state2) return scone_refuse(h, SCONE_EINVAL, who, "Adam / Adagrad need d_state2 (v / the sum of squares)");
   SCONE_ON_DEVICE(h);
   opt_args a;
   a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2, a.ctl = d_ctl;
   a.d_n = reinterpret_cast<const unsigned long long *>(d_n);
-  opt_scalars(cfg, &a.sc);
+  a.hyper = d_hyper;
+  a.sc = scone_opt_scalars{};
+  if (!with_hyper) opt_scalars(cfg, &a.sc);
   const unsigned blocks = opt_begin(h, n);
-  const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch_kind<decltype(F)::value>(h, cfg->kind, a, blocks, (hipStream_t)stream); });
+  const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch_kind<decltype(F)::value>(h, kind, a, blocks, (hipStream_t)stream); });
   if (bad) return scone_refuse(h, SCONE_EINVAL, who, "bad format");
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
@@ -236,4 +241,11 @@ extern "C" int scone_opt_step_dn(scone_handle *h, const scone_opt_cfg *cfg, cons
                                  const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_state1, float *d_state2,
                                  const scone_grad_ctl *d_ctl, scone_stream_t stream) {
   return opt_step(h, "scone_opt_step_dn", cfg, d_row_ids, d_grad_rows, n_cap, d_master, d_state1, d_state2, false, d_ctl, stream, true, d_n);
+}
+
+extern "C" int scone_opt_step_dh(scone_handle *h, int32_t kind, const int64_t *d_row_ids, const float *d_grad_rows, const uint64_t *d_n,
+                                 uint64_t n_cap, float *d_master, float *d_state1, float *d_state2, const scone_opt_hyper *d_hyper,
+                                 const scone_grad_ctl *d_ctl, void *stream) {
+  return opt_step(h, "scone_opt_step_dh", nullptr, d_row_ids, d_grad_rows, n_cap, d_master, d_state1, d_state2, false, d_ctl, stream, true,
+                  d_n, true, kind, d_hyper);
 }

@@ -12,6 +12,8 @@
 #include "scone_common.h"
 #include "scone_quant.h"
 
+#include <cmath>
+
 constexpr int OPT_NT = 4;  // pieces per lane and block: 4 x 64 x 4 = 1024 elements
 
 // ---- the host side both entry points open with
@@ -22,6 +24,18 @@ static inline int opt_need_table(scone_handle *h, const char *who, const char *b
   if (h->cfg.dim == 0) return scone_refuse(h, SCONE_EINVAL, who, "handle has no table (dim == 0)");
   if (!h->rows) return scone_refuse(h, SCONE_ESTATE, who, "handle has no table");
   return SCONE_OK;
+}
+// what scone_opt_step says of a cfg (null: nothing).  adam_needs_step false: scone_opt_hyper_init, whose step is the count of
+// steps already applied and is checked there
+static inline const char *opt_cfg_check(const scone_opt_cfg *cfg, bool adam_needs_step = true) {
+  if (!cfg) return "null cfg";
+  if (cfg->struct_size != sizeof(scone_opt_cfg)) return "cfg.struct_size does not match this library";
+  if (cfg->kind != SCONE_OPT_SGD && cfg->kind != SCONE_OPT_ADAGRAD && cfg->kind != SCONE_OPT_ADAM) return "bad kind";
+  if (!std::isfinite(cfg->lr) || !std::isfinite(cfg->beta1) || !std::isfinite(cfg->beta2) || !std::isfinite(cfg->eps) ||
+      !std::isfinite(cfg->weight_decay) || !std::isfinite(cfg->grad_scale))
+    return "lr, beta1, beta2, eps, weight_decay and grad_scale must be finite";
+  if (adam_needs_step && cfg->kind == SCONE_OPT_ADAM && cfg->step < 1) return "Adam needs step >= 1";
+  return nullptr;
 }
 // the table is about to change: as scone_table_store_f32_ids, the staged cache of cold rows is dropped.  Returns the grid for n
 // listed rows, a wave each (SCONE_OPT_MAX_BLOCKS caps it)
@@ -44,6 +58,36 @@ struct opt_n_device {
   __device__ __forceinline__ unsigned long long get() const {
     const unsigned long long n = *d_n;
     return n < n_cap ? n : n_cap;
+  }
+};
+
+// Where an optimizer kernel takes its scalars from.  opt_s_value: the launch, as ever (32 bytes of kernel arguments; the lean
+// step's seed and step are the lean_rand argument beside it).  opt_s_device (the _dh entry points): the scone_opt_hyper block an
+// earlier kernel of the stream (scone_opt_hyper_advance) left on the device.  Its address is a kernel argument and its fields
+// are wave-uniform: every wave loads them once, before the row loop and before its first store, as *d_n is read.  load() is
+// false when the block says the step was not applied: the wave then ends before it touches anything.  (The compiler keeps the
+// eight scalars' load behind that branch, whatever order the source states: a wave of the _dh kernels waits for one more
+// scalar-load round trip than a wave of the _dn kernels before its first row -- 0.4 us of a 22 us launch, nothing at size.)
+struct opt_s_value {
+  scone_opt_scalars sc;
+  __device__ __forceinline__ bool load(scone_opt_scalars &out) const {
+    out = sc;
+    return true;
+  }
+  template <typename RND>
+  __device__ __forceinline__ void rand(RND &) const {}
+};
+struct opt_s_device {
+  const scone_opt_hyper *__restrict__ hy;
+  __device__ __forceinline__ bool load(scone_opt_scalars &out) const {
+    if (hy->applied == 0u) return false;
+    out = hy->sc;
+    return true;
+  }
+  template <typename RND>
+  __device__ __forceinline__ void rand(RND &r) const {
+    r.seed = hy->seed;
+    r.step = hy->step;
   }
 };
 

@@ -384,6 +384,57 @@ def lean_rand16(seed: int, step: int, row_id: int, col: int) -> int:
     return int(L.lib().scone_lean_rand16(int(seed), int(step), int(row_id), int(col)))
 
 
+def opt_hyper_scalars(kind, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, step=1) -> dict:
+    """``scone_opt_hyper_scalars_of``: the host copy of what ``scone_opt_hyper_advance`` derives on the device at ``t = step`` --
+    :func:`opt_scalars` in every field but Adam's ``alpha``, which uses the header's integer power instead of libm's ``pow`` (at
+    most one fp32 ulp apart).  Runs without a GPU; ``ValueError`` for what the library refuses."""
+    out = L.OptScalars()
+    rc = L.lib().scone_opt_hyper_scalars_of(C.byref(_opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step)), C.byref(out))
+    if rc != L.OK:
+        _raise(rc, "scone_opt_hyper_scalars_of: bad kind, step < 1 for Adam, or a hyper-parameter that is not finite")
+    return {name: np.float32(getattr(out, name)) for name, _ in L.OptScalars._fields_}
+
+
+def _no_scalars_beside_hyper(who: str, given: dict) -> None:
+    """``hyper=`` replaces the by-value scalars: giving both is a ``ValueError``."""
+    both = [name for name, v in given.items() if v is not None]
+    if both:
+        raise ValueError(f"{who}: hyper= holds the hyper-parameters on the device; {', '.join(name + '=' for name in both)} beside it "
+                         "would be ignored -- write the block instead (hyper.lr.fill_(...), hyper.grad_scale.copy_(...))")
+
+
+class OptHyper:
+    """``scone_opt_hyper``: the 104 device bytes that hold an optimizer's hyper-parameters and its step count
+    (include/scone_hip.h, "optimizer hyper-parameters on the device"); :meth:`SconeTable.opt_hyper` makes one.  ``lr``,
+    ``beta1``, ``beta2``, ``eps``, ``weight_decay``, ``grad_scale`` (float64), ``step`` and ``seed`` (int64: the seed's 64 bits)
+    are 0-dim tensors that VIEW the block: ``hyper.lr.copy_(device_scalar)`` or ``hyper.lr.fill_(x)`` between steps -- or between
+    replays of a captured step -- is stream-ordered device work and changes what the next
+    :meth:`SconeTable.opt_hyper_advance` derives.  ``applied`` and ``bad`` (int32 views) are what the last advance left.
+    :meth:`read` synchronises."""
+
+    _INPUTS = ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale")
+
+    def __init__(self, device: torch.device) -> None:
+        self.buf = torch.zeros(C.sizeof(L.SconeOptHyper) // 8, dtype=torch.float64, device=device)   # 104 bytes, 8-byte aligned
+        for name in self._INPUTS:
+            setattr(self, name, self.buf[getattr(L.SconeOptHyper, name).offset // 8])
+        as_int = self.buf.view(torch.int64)
+        self.seed = as_int[L.SconeOptHyper.seed.offset // 8]
+        self.step = as_int[L.SconeOptHyper.step.offset // 8]
+        as_i32 = self.buf.view(torch.int32)
+        self.applied = as_i32[L.SconeOptHyper.applied.offset // 4]
+        self.bad = as_i32[L.SconeOptHyper.bad.offset // 4]
+
+    def read(self) -> dict:
+        """Every field on the host: the six doubles, ``seed``, ``step``, ``sc`` (a dict of eight ``np.float32``), ``applied``
+        and ``bad``.  Synchronises."""
+        rec = L.SconeOptHyper.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+        out = {name: float(getattr(rec, name)) for name in self._INPUTS}
+        out.update(seed=int(rec.seed), step=int(rec.step), applied=int(rec.applied), bad=int(rec.bad),
+                   sc={name: np.float32(getattr(rec.sc, name)) for name, _ in L.OptScalars._fields_})
+        return out
+
+
 class GradCtl:
     """``scone_grad_ctl``: the 24 device bytes :meth:`SconeTable.grad_ctl` fills and ``opt_step(..., ctl=)`` /
     ``opt_step_lean(..., ctl=)`` read (include/scone_hip.h, "gradient norm, clipping and skipped steps").  ``coef`` (fp32) and
@@ -1419,14 +1470,51 @@ class SconeTable:
             grad_rows.record_stream(stream)                        # it may be a temporary of the caller
         return sq, scratch[:n]
 
-    def grad_ctl(self, terms, grad_scale: float = 1.0, max_norm: Optional[float] = None, skip_nonfinite: bool = False,
-                 out: Optional[GradCtl] = None) -> GradCtl:
+    def opt_hyper(self, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
+                  seed: int = 0, step: int = 0, out: Optional[OptHyper] = None) -> OptHyper:
+        """``scone_opt_hyper_init``: an :class:`OptHyper` on the table's device holding these hyper-parameters, ``seed`` (stochastic
+        rounding) and ``step``, the number of steps ALREADY applied (0 for a fresh optimizer).  One launch on the current stream;
+        no synchronisation.  ``out``: a block to re-initialise instead of a fresh one."""
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits")
+        cfg = _opt_cfg(L.OPT_SGD, lr, betas, eps, weight_decay, grad_scale, step)
+        hyper = OptHyper(self.device) if out is None else out
+        with torch.cuda.device(self.device):
+            rc = L.lib().scone_opt_hyper_init(self._h, C.byref(cfg), int(seed), _ptr(hyper.buf),
+                                              torch.cuda.current_stream(self.device).cuda_stream)
+        self._check(rc, "scone_opt_hyper_init")
+        return hyper
+
+    def opt_hyper_advance(self, hyper: OptHyper, kind, ctl: Optional["GradCtl"] = None) -> None:
+        """``scone_opt_hyper_advance``: count one optimizer step in ``hyper`` and derive the fp32 scalars of ``kind`` (``"sgd"``,
+        ``"adagrad"``, ``"adam"``; the lean kinds advance as ``"sgd"``) on the device -- once per step, before the
+        ``opt_step(..., hyper=)`` / ``opt_step_lean(..., hyper=)`` calls of every table or shard that shares the block.  With
+        ``ctl`` whose ``skip`` is set nothing is counted and the steps behind it change nothing; a hyper-parameter that is not
+        finite sets ``hyper.bad`` instead.  One launch on the current stream; no synchronisation."""
+        if isinstance(kind, str):
+            k = kind.lower()
+            if k not in _OPT and k not in _LEAN:
+                raise ValueError(f"unknown optimizer kind {kind!r} (sgd, adagrad, adam, rowwise_adagrad)")
+            kind = _OPT.get(k, L.OPT_SGD)
+        with torch.cuda.device(self.device):
+            rc = L.lib().scone_opt_hyper_advance(self._h, int(kind), _ptr(hyper.buf), None if ctl is None else _ptr(ctl.buf),
+                                                 torch.cuda.current_stream(self.device).cuda_stream)
+        self._check(rc, "scone_opt_hyper_advance")
+
+    def grad_ctl(self, terms, grad_scale: Optional[float] = None, max_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 out: Optional[GradCtl] = None, hyper: Optional[OptHyper] = None) -> GradCtl:
         """``scone_grad_ctl_set``: a :class:`GradCtl` from squared-norm ``terms`` that stay on the device -- a sequence of 0-dim
         tensors (``grad_sqnorm``'s ``sq``, the dense parameters' squared norm, other shards') and floats, or one 1-D tensor; they
         are added in the order given, in double.  ``grad_scale`` is the un-scaling factor the step will use (the norm is that of
         the un-scaled gradient); ``max_norm=None`` does not clip; ``skip_nonfinite`` sets the block's ``skip`` when the sum is inf
         or NaN.  One launch on the current stream; no synchronisation.  ``out``: a :class:`GradCtl` to fill instead of a fresh one
-        (a captured step keeps one)."""
+        (a captured step keeps one).  ``hyper`` (an :class:`OptHyper`): ``scone_grad_ctl_set_dh`` -- ``grad_scale`` is read from the
+        block on the device (the same bits; a scale that is not finite there sets ``skip``); ``grad_scale=`` beside it is a
+        ``ValueError``."""
+        if hyper is not None:
+            _no_scalars_beside_hyper("grad_ctl", {"grad_scale": grad_scale})
+        elif grad_scale is None:
+            grad_scale = 1.0
         if not isinstance(terms, torch.Tensor):
             terms = list(terms)
         if isinstance(terms, torch.Tensor):
@@ -1442,18 +1530,24 @@ class SconeTable:
         ctl = GradCtl(self.device) if out is None else out
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            rc = L.lib().scone_grad_ctl_set(self._h, _ptr(vec) if vec.numel() else None, vec.numel(), float(grad_scale),
-                                            float("inf") if max_norm is None else float(max_norm), int(bool(skip_nonfinite)),
-                                            _ptr(ctl.buf), stream.cuda_stream)
-        self._check(rc, "scone_grad_ctl_set")
+            if hyper is None:
+                rc = L.lib().scone_grad_ctl_set(self._h, _ptr(vec) if vec.numel() else None, vec.numel(), float(grad_scale),
+                                                float("inf") if max_norm is None else float(max_norm), int(bool(skip_nonfinite)),
+                                                _ptr(ctl.buf), stream.cuda_stream)
+            else:
+                rc = L.lib().scone_grad_ctl_set_dh(self._h, _ptr(vec) if vec.numel() else None, vec.numel(), _ptr(hyper.buf),
+                                                   float("inf") if max_norm is None else float(max_norm),
+                                                   int(bool(skip_nonfinite)), _ptr(ctl.buf), stream.cuda_stream)
+        self._check(rc, "scone_grad_ctl_set" if hyper is None else "scone_grad_ctl_set_dh")
         if vec.numel() and out is None:                            # (out=: the caller keeps the block, and its terms with it)
             vec.record_stream(stream)
         return ctl
 
-    def opt_step(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, master: torch.Tensor, *, kind, lr: float, step: int = 1,
-                 state1: Optional[torch.Tensor] = None, state2: Optional[torch.Tensor] = None, betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0, ctl: Optional["GradCtl"] = None,
-                 n: Optional[torch.Tensor] = None) -> None:
+    def opt_step(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, master: torch.Tensor, *, kind, lr: Optional[float] = None,
+                 step: Optional[int] = None, state1: Optional[torch.Tensor] = None, state2: Optional[torch.Tensor] = None,
+                 betas=None, eps: Optional[float] = None, weight_decay: Optional[float] = None,
+                 grad_scale: Optional[float] = None, ctl: Optional["GradCtl"] = None, n: Optional[torch.Tensor] = None,
+                 hyper: Optional[OptHyper] = None) -> None:
         """``scone_opt_step``: the fused sparse optimizer step (include/scone_hip.h, "optimizer step").  ``row_ids`` ``[U]``
         int64 ascending and distinct and ``grad_rows`` ``[U, d]`` fp32 are what :meth:`BackwardPlan.rows` returns.  ``master``,
         ``state1`` (Adam's m) and ``state2`` (Adam's v / Adagrad's sum of squares) are fp32 ``[row_end - row_begin, d]``,
@@ -1463,8 +1557,22 @@ class SconeTable:
         ``coef`` and changes nothing at all when its ``skip`` is set.  ``n`` (a 1-element int64 device tensor,
         :meth:`BackwardContext.rows`' third result): ``scone_opt_step_dn`` -- the step over the first ``min(n, U)`` listed rows,
         ``U`` now the capacity of the two buffers; the count is read on the device.  Under capture a replay repeats Adam's
-        ``step`` as captured."""
-        cfg = _opt_cfg(kind, lr, betas, eps, weight_decay, grad_scale, step)
+        ``step`` as captured.  ``hyper`` (an :class:`OptHyper`, with ``n``): ``scone_opt_step_dh`` -- the scalars are those
+        :meth:`opt_hyper_advance` left in the block, read on the device; the step changes nothing if that advance did not apply.
+        ``lr`` (required without ``hyper``), ``step`` (1), ``betas`` ((0.9, 0.999)), ``eps`` (1e-8), ``weight_decay`` (0) and
+        ``grad_scale`` (1) are the by-value scalars: any of them beside ``hyper=`` is a ``ValueError``."""
+        if hyper is not None:
+            _no_scalars_beside_hyper("opt_step", dict(lr=lr, step=step, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                      grad_scale=grad_scale))
+            if n is None:
+                raise ValueError("opt_step: hyper= needs n= (a 1-element int64 device tensor that holds the row count)")
+            cfg = _opt_cfg(kind, 0.0, (0.0, 0.0), 0.0, 0.0, 1.0, 1)        # the kind only
+        else:
+            if lr is None:
+                raise ValueError("opt_step: lr is required (or hyper=)")
+            cfg = _opt_cfg(kind, lr, (0.9, 0.999) if betas is None else betas, 1e-8 if eps is None else eps,
+                           0.0 if weight_decay is None else weight_decay, 1.0 if grad_scale is None else grad_scale,
+                           1 if step is None else step)
         owned = self.row_end - self.row_begin
         for name, t, needed in (("master", master, True), ("state1", state1, cfg.kind == L.OPT_ADAM),
                                 ("state2", state2, cfg.kind in (L.OPT_ADAM, L.OPT_ADAGRAD))):
@@ -1486,10 +1594,16 @@ class SconeTable:
         if n is not None:
             n = _device_count("opt_step", n, self.device)
             with torch.cuda.device(self.device):
-                rc = L.lib().scone_opt_step_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
-                                               _ptr(master), _ptr(state1), _ptr(state2), None if ctl is None else _ptr(ctl.buf),
-                                               torch.cuda.current_stream(self.device).cuda_stream)
-            self._check(rc, "scone_opt_step_dn")
+                if hyper is not None:
+                    rc = L.lib().scone_opt_step_dh(self._h, cfg.kind, _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
+                                                   _ptr(master), _ptr(state1), _ptr(state2), _ptr(hyper.buf),
+                                                   None if ctl is None else _ptr(ctl.buf),
+                                                   torch.cuda.current_stream(self.device).cuda_stream)
+                else:
+                    rc = L.lib().scone_opt_step_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
+                                                   _ptr(master), _ptr(state1), _ptr(state2), None if ctl is None else _ptr(ctl.buf),
+                                                   torch.cuda.current_stream(self.device).cuda_stream)
+            self._check(rc, "scone_opt_step_dn" if hyper is None else "scone_opt_step_dh")
             return
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
@@ -1504,10 +1618,11 @@ class SconeTable:
             row_ids.record_stream(stream)
             grad_rows.record_stream(stream)
 
-    def opt_step_lean(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, *, kind, lr: float, master: Optional[torch.Tensor] = None,
-                      row_state: Optional[torch.Tensor] = None, eps: float = 1e-10, weight_decay: float = 0.0,
-                      grad_scale: float = 1.0, rounding="nearest", seed: int = 0, step: int = 1,
-                      ctl: Optional["GradCtl"] = None, n: Optional[torch.Tensor] = None) -> None:
+    def opt_step_lean(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, *, kind, lr: Optional[float] = None,
+                      master: Optional[torch.Tensor] = None, row_state: Optional[torch.Tensor] = None, eps: Optional[float] = None,
+                      weight_decay: Optional[float] = None, grad_scale: Optional[float] = None, rounding="nearest",
+                      seed: Optional[int] = None, step: Optional[int] = None, ctl: Optional["GradCtl"] = None,
+                      n: Optional[torch.Tensor] = None, hyper: Optional[OptHyper] = None) -> None:
         """``scone_opt_step_lean``: the lean optimizer step (include/scone_hip.h, "lean optimizer step").  ``kind``: ``"sgd"`` or
         ``"rowwise_adagrad"`` (ONE fp32 accumulator per row: ``row_state``, fp32 ``[row_end - row_begin]``, contiguous, on the
         table's device, updated in place).  ``master`` given (fp32 ``[row_end - row_begin, d]``): it is updated in place and
@@ -1516,8 +1631,22 @@ class SconeTable:
         ``seed``, ``step``, the global row id and the column).  One kernel launch on the current stream; no synchronisation.
         ``ctl`` (a :class:`GradCtl`): ``scone_opt_step_lean_ctl``, as for :meth:`opt_step`.  ``n`` (a 1-element int64 device
         tensor): ``scone_opt_step_lean_dn``, as for :meth:`opt_step`; under capture a replay repeats the stochastic rounding's
-        ``step`` as captured."""
-        cfg = _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step)
+        ``step`` as captured.  ``hyper`` (an :class:`OptHyper`, with ``n``): ``scone_opt_step_lean_dh`` -- the scalars, and the
+        random bits' ``seed`` and ``step``, are read from the block on the device, as for :meth:`opt_step`.  ``lr`` (required
+        without ``hyper``), ``eps`` (1e-10), ``weight_decay`` (0), ``grad_scale`` (1), ``seed`` (0) and ``step`` (1) are the by-value
+        scalars: any of them beside ``hyper=`` is a ``ValueError``."""
+        if hyper is not None:
+            _no_scalars_beside_hyper("opt_step_lean", dict(lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, seed=seed,
+                                                           step=step))
+            if n is None:
+                raise ValueError("opt_step_lean: hyper= needs n= (a 1-element int64 device tensor that holds the row count)")
+            cfg = _lean_cfg(kind, 0.0, 0.0, 0.0, 1.0, rounding, 0, 1)       # kind and rounding only
+        else:
+            if lr is None:
+                raise ValueError("opt_step_lean: lr is required (or hyper=)")
+            cfg = _lean_cfg(kind, lr, 1e-10 if eps is None else eps, 0.0 if weight_decay is None else weight_decay,
+                            1.0 if grad_scale is None else grad_scale, rounding, 0 if seed is None else seed,
+                            1 if step is None else step)
         owned = self.row_end - self.row_begin
         if master is None and self.fmt not in (L.FMT_F32, L.FMT_BF16):
             raise ValueError("opt_step_lean: in place (master=None) needs an fp32 or bf16 table, this one has format code "
@@ -1545,10 +1674,16 @@ class SconeTable:
         if n is not None:
             n = _device_count("opt_step_lean", n, self.device)
             with torch.cuda.device(self.device):
-                rc = L.lib().scone_opt_step_lean_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
-                                                    _ptr(master), _ptr(row_state), None if ctl is None else _ptr(ctl.buf),
-                                                    torch.cuda.current_stream(self.device).cuda_stream)
-            self._check(rc, "scone_opt_step_lean_dn")
+                if hyper is not None:
+                    rc = L.lib().scone_opt_step_lean_dh(self._h, cfg.kind, cfg.rounding, _ptr(row_ids), _ptr(grad_rows), _ptr(n),
+                                                        row_ids.numel(), _ptr(master), _ptr(row_state), _ptr(hyper.buf),
+                                                        None if ctl is None else _ptr(ctl.buf),
+                                                        torch.cuda.current_stream(self.device).cuda_stream)
+                else:
+                    rc = L.lib().scone_opt_step_lean_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
+                                                        _ptr(master), _ptr(row_state), None if ctl is None else _ptr(ctl.buf),
+                                                        torch.cuda.current_stream(self.device).cuda_stream)
+            self._check(rc, "scone_opt_step_lean_dn" if hyper is None else "scone_opt_step_lean_dh")
             return
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)

@@ -303,10 +303,24 @@ class FGramOptimizer:
     gradient accumulation over micro-batches needs the default road (where a second backward adds to the gradient on the device:
     include/scone_hip.h, "gradient accumulation").  ``step()`` only returns the number of rows updated since
     the last ``step()`` (its ``grad_scale`` argument is not used) and ``zero_grad()`` has nothing to do.  One backward of this
-    road leaves the bits one backward + ``step(grad_scale)`` of the default road leaves."""
+    road leaves the bits one backward + ``step(grad_scale)`` of the default road leaves.
+
+    ``capturable=True`` (include/scone_hip.h, "optimizer hyper-parameters on the device"; what ``torch.optim.Adam(capturable=True)``
+    is to Adam).  ``lr``, ``betas``, ``eps``, ``weight_decay``, the gradient scale, ``seed`` and the step count ``t`` live in a
+    104-byte block on the device, ``opt.hyper`` (an :class:`~scone_amd.hip_backend.OptHyper`): ``step()`` advances the count and
+    derives the kernels' scalars ON THE DEVICE (``scone_opt_hyper_advance``) and the update reads them there (``scone_opt_step_dh``
+    / ``scone_opt_step_lean_dh``), in static and in non-static mode.  So every kind and ``rounding="stochastic"`` can be captured
+    with a module built with ``static_rows=``, a replay counts its own step, and a schedule or a dynamic loss scale is a device
+    write between replays: ``opt.hyper.lr.copy_(device_scalar)``, ``step(grad_scale=device_scalar)``.  Assigning ``opt.lr``,
+    ``opt.weight_decay``, ``opt.eps``, ``opt.betas`` or ``opt.t`` enqueues the write; READING ``opt.t`` SYNCHRONISES (it reads the
+    device).  ``t`` does NOT advance on a step the device skipped (``skip_nonfinite=True``).  Adam's step size uses the header's
+    integer power in place of ``pow``: at most one fp32 ulp from the default road's, and the same bits wherever the header lists.
+    Not with ``fused_backward=True`` (``ValueError``)."""
 
     def __init__(self, module, kind: str = "adam", lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, rounding: str = "nearest", seed: int = 0, fused_backward: bool = False) -> None:
+                 weight_decay: float = 0.0, rounding: str = "nearest", seed: int = 0, fused_backward: bool = False,
+                 capturable: bool = False) -> None:
+        self.capturable, self.hyper = False, None      # until the block exists the setters below only keep the host's copy
         self.in_place = isinstance(module, InPlaceFGramTable)
         kinds = ("sgd", "rowwise_adagrad") if self.in_place else ("sgd", "adagrad", "adam", "rowwise_adagrad")
         if kind not in kinds:
@@ -322,6 +336,9 @@ class FGramOptimizer:
                 raise ValueError("stochastic rounding is for bf16 rows: an fp32 row has nothing to round")
         elif rounding == "stochastic":
             raise ValueError("stochastic rounding is for an InPlaceFGramTable: a master copy has nothing to round")
+        if capturable and fused_backward:
+            raise ValueError("capturable=True and fused_backward=True do not go together (scone_backward_apply_lean takes its "
+                             "hyper-parameters by value)")
         self.module, self.kind = module, kind
         self.rounding, self.seed = rounding, int(seed)
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
@@ -334,9 +351,76 @@ class FGramOptimizer:
         self.state2: Optional[torch.Tensor] = None     # Adam's v / Adagrad's sum of squares
         self.last_ctl = None                           # the GradCtl of the last clipped / guarded step()
         self._static_ctl = self._static_sq = self._static_scratch = None    # static mode: kept across steps (and replays)
+        if capturable:
+            table = module.cache.to_device()
+            self._n_word = torch.zeros(1, dtype=torch.int64, device=table.device)   # non-static mode: the row count, for the _dh calls
+            self.capturable = True
+            self._init_hyper(0)
+
+    def _init_hyper(self, t: int) -> None:
+        """(Re-)initialise the device block from the host's copies and ``t`` steps already applied (``scone_opt_hyper_init``)."""
+        self.hyper = self.module.cache.to_device().opt_hyper(lr=self._lr, betas=self._betas, eps=self._eps,
+                                                             weight_decay=self._weight_decay, grad_scale=1.0, seed=self.seed,
+                                                             step=int(t), out=self.hyper)
+
+    # lr, betas, eps, weight_decay and t are plain values on the default road; with capturable=True an assignment also enqueues
+    # the write into the device block, and t is read from there
+    def _put(self, field: str, value) -> None:
+        if self.hyper is not None:
+            getattr(self.hyper, field).fill_(value)
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value) -> None:
+        self._lr = float(value)
+        self._put("lr", self._lr)
+
+    @property
+    def eps(self) -> float:
+        return self._eps
+
+    @eps.setter
+    def eps(self, value) -> None:
+        self._eps = float(value)
+        self._put("eps", self._eps)
+
+    @property
+    def weight_decay(self) -> float:
+        return self._weight_decay
+
+    @weight_decay.setter
+    def weight_decay(self, value) -> None:
+        self._weight_decay = float(value)
+        self._put("weight_decay", self._weight_decay)
+
+    @property
+    def betas(self):
+        return self._betas
+
+    @betas.setter
+    def betas(self, value) -> None:
+        self._betas = (float(value[0]), float(value[1]))
+        self._put("beta1", self._betas[0])
+        self._put("beta2", self._betas[1])
+
+    @property
+    def t(self) -> int:
+        """The number of steps applied.  ``capturable=True``: read from the device -- SYNCHRONISES."""
+        return int(self.hyper.step.item()) if self.hyper is not None else self._t
+
+    @t.setter
+    def t(self, value) -> None:
+        self._t = int(value)
+        self._put("step", self._t)
 
     def _set_fused(self, on: bool) -> None:
         on = bool(on)
+        if on and self.capturable:
+            raise ValueError("capturable=True and fused_backward=True do not go together (scone_backward_apply_lean takes its "
+                             "hyper-parameters by value)")
         if on:
             if getattr(self.module, "_static", None) is not None:
                 raise ValueError("fused_backward=True and a module built with static_rows= do not go together "
@@ -472,6 +556,74 @@ class FGramOptimizer:
             module._touched = []                         # the served table is current: commit() has nothing to store
         return int(ids.numel())
 
+    def _step_hyper(self, static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite) -> int:
+        """``step()`` with ``capturable=True``: ``grad_ctl(hyper=)``, ``opt_hyper_advance``, then the ``_dh`` step -- every scalar
+        is read on the device.  ``static``: the triple of a static backward, or ``None`` (the gradient on the module; its row count
+        goes into a device word the optimizer keeps)."""
+        module = self.module
+        table = module.cache.to_device()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if static is not None:
+            ids, rows, n = static
+        else:
+            if capturing:
+                raise ValueError("FGramOptimizer.step under capture needs a module built with static_rows= (the default backward "
+                                 "synchronises)")
+            grad = self._current_grad()
+            if grad is None:
+                return 0
+            ids, rows = grad
+            ids, rows = ids.contiguous(), rows.contiguous()
+            n = self._n_word.fill_(ids.numel())
+        if capturing and (not self._static_state_ready() or (ctl_road and self._static_ctl is None)):
+            raise ValueError("FGramOptimizer.step under capture: the optimizer state is allocated at the first step; run one "
+                             "step eagerly (the warm-up) before capturing")
+        if isinstance(grad_scale, torch.Tensor):
+            if grad_scale.dtype != torch.float64 or grad_scale.numel() != 1 or grad_scale.device != table.device:
+                raise ValueError(f"FGramOptimizer.step: a grad_scale on the device must be one float64 on {table.device}")
+            self.hyper.grad_scale.copy_(grad_scale.reshape(()))
+        elif grad_scale is not None:
+            self.hyper.grad_scale.fill_(float(grad_scale))
+        ctl = None
+        if ctl_road:
+            from scone_amd.hip_backend import GradCtl
+            extra = [] if extra_sqnorm is None else (list(extra_sqnorm) if isinstance(extra_sqnorm, (list, tuple)) else [extra_sqnorm])
+            if static is not None:
+                if self._static_ctl is None:
+                    self._static_ctl = GradCtl(table.device)
+                    self._static_sq = torch.zeros((), dtype=torch.float64, device=table.device)
+                    self._static_scratch = torch.zeros(_lib.grad_sqnorm_scratch(rows.shape[0]), dtype=torch.float64,
+                                                       device=table.device)
+                sq = table.grad_sqnorm(rows, self._static_scratch, n=n, out=self._static_sq)[0]
+                out = self._static_ctl
+            else:
+                sq, out = table.grad_sqnorm(rows)[0], None
+            ctl = table.grad_ctl([sq, *extra], max_norm=max_norm, skip_nonfinite=skip_nonfinite, out=out, hyper=self.hyper)
+            self.last_ctl = ctl
+        table.opt_hyper_advance(self.hyper, self.kind, ctl)
+        self._ensure_state()
+        lo, hi = table.row_begin, table.row_end
+
+        def own(x):
+            return None if x is None else x[lo:hi]
+
+        if self.in_place:
+            table.opt_step_lean(ids, rows, kind=self.kind, row_state=own(self.state2), rounding=self.rounding, ctl=ctl, n=n,
+                                hyper=self.hyper)
+        elif self.kind == "rowwise_adagrad":
+            table.opt_step_lean(ids, rows, kind=self.kind, master=own(module.weight.detach()), row_state=own(self.state2), ctl=ctl,
+                                n=n, hyper=self.hyper)
+        else:
+            table.opt_step(ids, rows, own(module.weight.detach()), kind=self.kind, state1=own(self.state1), state2=own(self.state2),
+                           ctl=ctl, n=n, hyper=self.hyper)
+        if static is None:
+            stream = torch.cuda.current_stream(table.device)
+            ids.record_stream(stream)                    # they may be temporaries of the caller
+            rows.record_stream(stream)
+        if not self.in_place:
+            module._touched = []                         # the served table is current: commit() has nothing to store
+        return int(ids.numel())
+
     def found_nonfinite(self) -> bool:
         """Whether the last ``step(...)`` that took a clipping / skipping argument found inf or NaN and skipped (with
         ``skip_nonfinite=True``; without it nothing is ever skipped).  SYNCHRONISES: it reads ``last_ctl.skip``.  For the loss
@@ -492,18 +644,25 @@ class FGramOptimizer:
         parameters', other shards'), at the SAME loss scale -- a 0-dim device tensor, a float, or a sequence of them.
         ``skip_nonfinite=True`` skips the step if any term is inf or NaN.  ``t`` ADVANCES ON A DEVICE-SKIPPED STEP TOO: the
         host does not know the outcome.  A caller who wants Adam's ``t`` unchanged by a skipped step calls
-        :meth:`found_nonfinite` (a synchronise) and sets ``opt.t -= 1``.  With none of the three set, the step is the plain
-        one.
+        :meth:`found_nonfinite` (a synchronise) and sets ``opt.t -= 1``.  With ``capturable=True`` there is nothing to correct:
+        the count is on the device and ``t`` does NOT advance on a device-skipped step.  With none of the three set, the step is
+        the plain one.
+
+        ``capturable=True``: ``grad_scale`` is a float, a 0-dim float64 tensor on the table's device (copied into the block
+        without a synchronise: a dynamic loss scale), or ``None`` (the block's ``hyper.grad_scale`` as it stands).  A
+        hyper-parameter that is not finite on the device declines the step and sets ``hyper.bad``.
 
         Static mode (a module built with ``static_rows=``): the gradient is ``module.static_grad``, whose row count is on the
         device; the ``_dn`` calls read it there, the norm's scratch and the control block are kept on the optimizer, and nothing
         synchronises or allocates after the first step -- the step can be captured.  Returns the buffers' capacity (the count
         itself is ``module.static_grad[2]``).  While the stream is capturing, ``kind="adam"`` and ``rounding="stochastic"`` are
         refused (``ValueError``): their step-dependent scalars are launch arguments, which a replay repeats as captured.
-        Eagerly both work.  A backward that overflowed ``static_rows`` left ``n = 0``: the step changes nothing
-        (:meth:`rows_overflowed`)."""
+        Eagerly both work; with ``capturable=True`` both are captured.  A backward that overflowed ``static_rows`` left
+        ``n = 0``: the step changes nothing (:meth:`rows_overflowed`)."""
         ctl_road = max_norm is not None or extra_sqnorm is not None or bool(skip_nonfinite)
         static = getattr(self.module, "static_grad", None)
+        if self.capturable:
+            return self._step_hyper(static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite)
         if static is not None:
             return self._step_static(static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite)
         if self.fused_backward:
@@ -577,8 +736,14 @@ class FGramOptimizer:
                 torch.zeros((0, shape[1]), dtype=grad.dtype, device=grad.device), shape, is_coalesced=True)
 
     def state_dict(self) -> dict:
-        return {"kind": self.kind, "t": self.t, "lr": self.lr, "betas": self.betas, "eps": self.eps,
-                "weight_decay": self.weight_decay, "rounding": self.rounding, "seed": self.seed,
+        """``capturable=True``: ``t`` and the hyper-parameters are the DEVICE's (a synchronise): what a schedule wrote into
+        ``opt.hyper`` is what is saved."""
+        if self.capturable:
+            h = self.hyper.read()
+            self._lr, self._betas, self._eps, self._weight_decay = h["lr"], (h["beta1"], h["beta2"]), h["eps"], h["weight_decay"]
+            self._t = h["step"]
+        return {"kind": self.kind, "t": self._t, "lr": self.lr, "betas": self.betas, "eps": self.eps,
+                "weight_decay": self.weight_decay, "rounding": self.rounding, "seed": self.seed, "capturable": self.capturable,
                 "fused_backward": self.fused_backward, "grad_scale": self.grad_scale,
                 "state1": None if self.state1 is None else self.state1.clone(),
                 "state2": None if self.state2 is None else self.state2.clone()}
@@ -586,14 +751,17 @@ class FGramOptimizer:
     def load_state_dict(self, state: dict) -> None:
         if state["kind"] != self.kind:
             raise ValueError(f"state of a {state['kind']!r} optimizer loaded into a {self.kind!r} one")
-        self.t, self.lr, self.eps, self.weight_decay = int(state["t"]), float(state["lr"]), float(state["eps"]), float(state["weight_decay"])
-        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        # (a state saved with either value of capturable loads into either optimizer: the mode is the constructor's)
+        self._t, self._lr, self._eps, self._weight_decay = int(state["t"]), float(state["lr"]), float(state["eps"]), float(state["weight_decay"])
+        self._betas = (float(state["betas"][0]), float(state["betas"][1]))
         rounding = state.get("rounding", "nearest")
         if rounding == "stochastic" and not (self.in_place and self.module.cache.to_device().fmt == _lib.FMT_BF16):
             raise ValueError("a state with stochastic rounding is for an InPlaceFGramTable on a bf16 cache")
         self.rounding, self.seed = rounding, int(state.get("seed", 0))
         self._set_fused(state.get("fused_backward", False))
         self.grad_scale = float(state.get("grad_scale", 1.0))
+        if self.capturable:
+            self._init_hyper(self._t)                    # the block: these values, seed, and t steps already applied
         table = self.module.cache.to_device()
         shape = (table.n_rows,) if self.kind == "rowwise_adagrad" else (table.n_rows, table.dim)
         for name in ("state1", "state2"):
