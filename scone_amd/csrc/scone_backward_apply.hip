@@ -380,11 +380,7 @@ extern "C" int scone_backward_apply_lean(scone_handle *h, scone_bwd_plan *plan, 
   if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM) return scone_refuse(h, SCONE_EINVAL, who, "bad reduce");
   const int fmt = h->cfg.table_fmt;
   const bool stoch = cfg->rounding == SCONE_ROUND_STOCHASTIC;
-  if (fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
-    return scone_refuse(h, SCONE_EINVAL, who,
-                        (std::string("in place needs an fp32 or bf16 table, this one is ") + scone_fmt_name(fmt)).c_str());
-  if (stoch && fmt != SCONE_FMT_BF16)
-    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding on an fp32 table: there is nothing to round");
+  SCONE_TRY(lean_inplace_check(h, who, stoch, false, false));
   if (h->cfg.dim > SCONE_BWD_APPLY_MAX_DIM)
     return scone_refuse(h, SCONE_EINVAL, who,
                         "d > 4096 is not fused (a wave's gradient row must fit its share of LDS): call scone_backward_rows, then "

@@ -149,38 +149,27 @@ void opt_scalars(const scone_opt_cfg *cfg, scone_opt_scalars *out) {
 struct opt_args {
   const int64_t *ids;
   const float *grad;
-  unsigned long long n;
-  scone_opt_scalars sc;
+  unsigned long long n;  // the row count; the cap of the count on the device in the _dn and _dh forms
+  scone_opt_scalars sc;  // by value; not read in the _dh form
   float *master, *s1, *s2;
-  const scone_grad_ctl *ctl;  // null: scone_opt_step
-  const unsigned long long *d_n;  // scone_opt_step_dn: the count on the device, n its cap; null: n by value
-  const scone_opt_hyper *hyper;   // scone_opt_step_dh: the scalars on the device (d_n is set too); null: sc by value
 };
 
-template <int FMT, int KIND>
-void opt_launch(scone_handle *h, const opt_args &a, unsigned blocks, hipStream_t s) {
-  if (a.hyper)
-    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_device, opt_s_device>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
-                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
-                       opt_s_device{a.hyper}, a.master, a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
-  else if (a.d_n)
-    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_device, opt_s_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
-                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
-                       opt_s_value{a.sc}, a.master, a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
-  else
-    hipLaunchKernelGGL((k_opt_step<FMT, KIND, opt_n_value, opt_s_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad, opt_n_value{a.n},
-                       (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, opt_s_value{a.sc}, a.master,
-                       a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
-}
-
+// the one launch site: the kind, then the sources of the call's form (scone_opt_rows.h), select the instantiation
 template <int FMT>
-void opt_launch_kind(scone_handle *h, int kind, const opt_args &a, unsigned blocks, hipStream_t s) {
+void opt_launch(scone_handle *h, int kind, const opt_call &c, const opt_args &a, unsigned blocks, hipStream_t s) {
+  auto launch = [&](auto K) {
+    opt_with_sources(c, a.n, a.sc, [&](auto nsrc, auto ssrc) {
+      hipLaunchKernelGGL((k_opt_step<FMT, decltype(K)::value, decltype(nsrc), decltype(ssrc)>), dim3(blocks), dim3(256), 0, s, a.ids,
+                         a.grad, nsrc, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim, ssrc,
+                         a.master, a.s1, a.s2, scone_store_of(h), (__half *)h->scales, h->d_status, c.d_ctl);
+    });
+  };
   if (kind == SCONE_OPT_SGD)
-    opt_launch<FMT, SCONE_OPT_SGD>(h, a, blocks, s);
+    launch(std::integral_constant<int, SCONE_OPT_SGD>());
   else if (kind == SCONE_OPT_ADAGRAD)
-    opt_launch<FMT, SCONE_OPT_ADAGRAD>(h, a, blocks, s);
+    launch(std::integral_constant<int, SCONE_OPT_ADAGRAD>());
   else
-    opt_launch<FMT, SCONE_OPT_ADAM>(h, a, blocks, s);
+    launch(std::integral_constant<int, SCONE_OPT_ADAM>());
 }
 
 }  // namespace
@@ -193,33 +182,25 @@ extern "C" int scone_opt_scalars_of(const scone_opt_cfg *cfg, scone_opt_scalars 
 
 namespace {
 
-// scone_opt_step (with_ctl false, ctl null), scone_opt_step_ctl, scone_opt_step_dn (with_n: n is the cap of *d_n) and
-// scone_opt_step_dh (with_hyper: cfg is null, the kind comes by value and the scalars from *d_hyper)
-int opt_step(scone_handle *h, const char *who, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
-             float *d_master, float *d_state1, float *d_state2, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream,
-             bool with_n = false, const uint64_t *d_n = nullptr, bool with_hyper = false, int32_t kind_dh = 0,
-             const scone_opt_hyper *d_hyper = nullptr) {
-  const int kind = with_hyper ? kind_dh : cfg ? cfg->kind : 0;
-  const char *bad_cfg = !with_hyper ? opt_cfg_check(cfg)
+// every form of scone_opt_step: c says which (scone_opt_rows.h); cfg is null in the _dh form, n the cap in the _dn and _dh forms
+int opt_step(scone_handle *h, const opt_call &c, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
+             float *d_master, float *d_state1, float *d_state2, scone_stream_t stream) {
+  const int kind = c.with_hyper ? c.kind : cfg ? cfg->kind : 0;
+  const char *bad_cfg = !c.with_hyper ? opt_cfg_check(cfg)
                         : kind != SCONE_OPT_SGD && kind != SCONE_OPT_ADAGRAD && kind != SCONE_OPT_ADAM ? "bad kind" : nullptr;
-  SCONE_TRY(opt_need_table(h, who, bad_cfg));
-  if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
-  if (with_n && !d_n) return scone_refuse(h, SCONE_EINVAL, who, "null d_n");
-  if (with_hyper && !d_hyper) return scone_refuse(h, SCONE_EINVAL, who, "null d_hyper");
+  SCONE_TRY(opt_open(h, c, bad_cfg));
   if (n == 0) return SCONE_OK;
-  if (!d_row_ids || !d_grad_rows || !d_master) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
-  if (kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, who, "Adam needs d_state1 (m)");
-  if (kind != SCONE_OPT_SGD && !d_state2) return scone_refuse(h, SCONE_EINVAL, who, "Adam / Adagrad need d_state2 (v / the sum of squares)");
+  if (!d_row_ids || !d_grad_rows || !d_master) return scone_refuse(h, SCONE_EINVAL, c.who, "null pointer");
+  if (kind == SCONE_OPT_ADAM && !d_state1) return scone_refuse(h, SCONE_EINVAL, c.who, "Adam needs d_state1 (m)");
+  if (kind != SCONE_OPT_SGD && !d_state2) return scone_refuse(h, SCONE_EINVAL, c.who, "Adam / Adagrad need d_state2 (v / the sum of squares)");
   SCONE_ON_DEVICE(h);
   opt_args a;
-  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2, a.ctl = d_ctl;
-  a.d_n = reinterpret_cast<const unsigned long long *>(d_n);
-  a.hyper = d_hyper;
+  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.s1 = d_state1, a.s2 = d_state2;
   a.sc = scone_opt_scalars{};
-  if (!with_hyper) opt_scalars(cfg, &a.sc);
+  if (!c.with_hyper) opt_scalars(cfg, &a.sc);
   const unsigned blocks = opt_begin(h, n);
-  const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch_kind<decltype(F)::value>(h, kind, a, blocks, (hipStream_t)stream); });
-  if (bad) return scone_refuse(h, SCONE_EINVAL, who, "bad format");
+  const int bad = scone_dispatch_fmt(h->cfg.table_fmt, [&](auto F) { opt_launch<decltype(F)::value>(h, kind, c, a, blocks, (hipStream_t)stream); });
+  if (bad) return scone_refuse(h, SCONE_EINVAL, c.who, "bad format");
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
 }
@@ -228,24 +209,27 @@ int opt_step(scone_handle *h, const char *who, const scone_opt_cfg *cfg, const i
 
 extern "C" int scone_opt_step(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows, uint64_t n,
                               float *d_master, float *d_state1, float *d_state2, scone_stream_t stream) {
-  return opt_step(h, "scone_opt_step", cfg, d_row_ids, d_grad_rows, n, d_master, d_state1, d_state2, false, nullptr, stream);
+  return opt_step(h, {.who = "scone_opt_step"}, cfg, d_row_ids, d_grad_rows, n, d_master, d_state1, d_state2, stream);
 }
 
 extern "C" int scone_opt_step_ctl(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                                   uint64_t n, float *d_master, float *d_state1, float *d_state2, const scone_grad_ctl *d_ctl,
                                   scone_stream_t stream) {
-  return opt_step(h, "scone_opt_step_ctl", cfg, d_row_ids, d_grad_rows, n, d_master, d_state1, d_state2, true, d_ctl, stream);
+  return opt_step(h, {.who = "scone_opt_step_ctl", .d_ctl = d_ctl, .need_ctl = true}, cfg, d_row_ids, d_grad_rows, n, d_master, d_state1,
+                  d_state2, stream);
 }
 
 extern "C" int scone_opt_step_dn(scone_handle *h, const scone_opt_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                                  const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_state1, float *d_state2,
                                  const scone_grad_ctl *d_ctl, scone_stream_t stream) {
-  return opt_step(h, "scone_opt_step_dn", cfg, d_row_ids, d_grad_rows, n_cap, d_master, d_state1, d_state2, false, d_ctl, stream, true, d_n);
+  return opt_step(h, {.who = "scone_opt_step_dn", .d_ctl = d_ctl, .d_n = d_n, .with_n = true}, cfg, d_row_ids, d_grad_rows, n_cap, d_master,
+                  d_state1, d_state2, stream);
 }
 
 extern "C" int scone_opt_step_dh(scone_handle *h, int32_t kind, const int64_t *d_row_ids, const float *d_grad_rows, const uint64_t *d_n,
                                  uint64_t n_cap, float *d_master, float *d_state1, float *d_state2, const scone_opt_hyper *d_hyper,
                                  const scone_grad_ctl *d_ctl, void *stream) {
-  return opt_step(h, "scone_opt_step_dh", nullptr, d_row_ids, d_grad_rows, n_cap, d_master, d_state1, d_state2, false, d_ctl, stream, true,
-                  d_n, true, kind, d_hyper);
+  return opt_step(h, {.who = "scone_opt_step_dh", .d_ctl = d_ctl, .d_n = d_n, .with_n = true, .d_hyper = d_hyper, .with_hyper = true,
+                      .kind = kind},
+                  nullptr, d_row_ids, d_grad_rows, n_cap, d_master, d_state1, d_state2, stream);
 }

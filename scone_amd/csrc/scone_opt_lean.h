@@ -63,6 +63,23 @@ static inline const char *lean_check(const scone_lean_cfg *cfg) {
   return nullptr;
 }
 
+// The mode refusals of a lean step, for the handle's table format: in place (no master) the rows must be fp32 or bf16, and only
+// in-place bf16 rows have anything to round.  master_wording: scone_opt_step_lean names its d_master argument in the first text;
+// scone_backward_apply_lean, which is always in place, has none
+static inline int lean_inplace_check(scone_handle *h, const char *who, bool stoch, bool has_master, bool master_wording) {
+  const int fmt = h->cfg.table_fmt;
+  if (!has_master && fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
+    return scone_refuse(h, SCONE_EINVAL, who,
+                        (std::string(master_wording ? "in place (d_master == NULL)" : "in place") +
+                         " needs an fp32 or bf16 table, this one is " + scone_fmt_name(fmt))
+                            .c_str());
+  if (stoch && has_master)
+    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding with a master: there is nothing to round");
+  if (stoch && fmt != SCONE_FMT_BF16)
+    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding on an fp32 table: there is nothing to round");
+  return SCONE_OK;
+}
+
 static inline void lean_scalars(const scone_lean_cfg *cfg, scone_opt_scalars *out) {
   *out = scone_opt_scalars{};
   out->alpha = (float)cfg->lr;

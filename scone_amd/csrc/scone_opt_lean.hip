@@ -148,37 +148,26 @@ __global__ __launch_bounds__(256) void k_opt_lean(const int64_t *__restrict__ id
 struct lean_args {
   const int64_t *ids;
   const float *grad;
-  unsigned long long n;
-  scone_opt_scalars sc;
+  unsigned long long n;  // the row count; the cap of the count on the device in the _dn and _dh forms
+  scone_opt_scalars sc;  // by value, with rnd's seed and step; not read in the _dh form
   lean_rand rnd;
   float *master, *row_state;
-  const scone_grad_ctl *ctl;  // null: scone_opt_step_lean
-  const unsigned long long *d_n;  // scone_opt_step_lean_dn: the count on the device, n its cap; null: n by value
-  const scone_opt_hyper *hyper;   // scone_opt_step_lean_dh: scalars, seed and step on the device (d_n is set too); null: by value
 };
 
-template <int FMT, int KIND, bool INPLACE, bool STOCH>
-void lean_launch(scone_handle *h, const lean_args &a, unsigned blocks, hipStream_t s) {
-  if (a.hyper)
-    hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH, opt_n_device, opt_s_device>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
-                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
-                       opt_s_device{a.hyper}, a.rnd, a.master, a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
-  else if (a.d_n)
-    hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH, opt_n_device, opt_s_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
-                       opt_n_device{a.d_n, a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
-                       opt_s_value{a.sc}, a.rnd, a.master, a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
-  else
-    hipLaunchKernelGGL((k_opt_lean<FMT, KIND, INPLACE, STOCH, opt_n_value, opt_s_value>), dim3(blocks), dim3(256), 0, s, a.ids, a.grad,
-                       opt_n_value{a.n}, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end, h->cfg.dim,
-                       opt_s_value{a.sc}, a.rnd, a.master, a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, a.ctl);
-}
-
+// the one launch site: the kind, then the sources of the call's form (scone_opt_rows.h), select the instantiation
 template <int FMT, bool INPLACE, bool STOCH>
-void lean_launch_kind(scone_handle *h, int kind, const lean_args &a, unsigned blocks, hipStream_t s) {
+void lean_launch(scone_handle *h, int kind, const opt_call &c, const lean_args &a, unsigned blocks, hipStream_t s) {
+  auto launch = [&](auto K) {
+    opt_with_sources(c, a.n, a.sc, [&](auto nsrc, auto ssrc) {
+      hipLaunchKernelGGL((k_opt_lean<FMT, decltype(K)::value, INPLACE, STOCH, decltype(nsrc), decltype(ssrc)>), dim3(blocks), dim3(256),
+                         0, s, a.ids, a.grad, nsrc, (unsigned long long)h->cfg.row_begin, (unsigned long long)h->cfg.row_end,
+                         h->cfg.dim, ssrc, a.rnd, a.master, a.row_state, scone_store_of(h), (__half *)h->scales, h->d_status, c.d_ctl);
+    });
+  };
   if (kind == SCONE_LEAN_SGD)
-    lean_launch<FMT, SCONE_LEAN_SGD, INPLACE, STOCH>(h, a, blocks, s);
+    launch(std::integral_constant<int, SCONE_LEAN_SGD>());
   else
-    lean_launch<FMT, SCONE_LEAN_ROWWISE_ADAGRAD, INPLACE, STOCH>(h, a, blocks, s);
+    launch(std::integral_constant<int, SCONE_LEAN_ROWWISE_ADAGRAD>());
 }
 
 }  // namespace
@@ -195,42 +184,28 @@ extern "C" uint32_t scone_lean_rand16(uint64_t seed, int64_t step, uint64_t row_
 
 namespace {
 
-// scone_opt_step_lean (with_ctl false, ctl null), scone_opt_step_lean_ctl, scone_opt_step_lean_dn (with_n: n is the cap of *d_n)
-// and scone_opt_step_lean_dh (with_hyper: cfg is null, kind and rounding come by value, the rest from *d_hyper)
-int opt_step_lean(scone_handle *h, const char *who, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
-                  uint64_t n, float *d_master, float *d_row_state, bool with_ctl, const scone_grad_ctl *d_ctl, scone_stream_t stream,
-                  bool with_n = false, const uint64_t *d_n = nullptr, bool with_hyper = false, int32_t kind_dh = 0,
-                  int32_t rounding_dh = 0, const scone_opt_hyper *d_hyper = nullptr) {
-  const int kind = with_hyper ? kind_dh : cfg ? cfg->kind : 0;
-  const int rounding = with_hyper ? rounding_dh : cfg ? cfg->rounding : 0;
-  const char *bad_cfg = !with_hyper ? lean_check(cfg)
+// every form of scone_opt_step_lean: c says which (scone_opt_rows.h); cfg is null in the _dh form, n the cap in the _dn and _dh forms
+int opt_step_lean(scone_handle *h, const opt_call &c, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
+                  uint64_t n, float *d_master, float *d_row_state, scone_stream_t stream) {
+  const int kind = c.with_hyper ? c.kind : cfg ? cfg->kind : 0;
+  const int rounding = c.with_hyper ? c.rounding : cfg ? cfg->rounding : 0;
+  const char *bad_cfg = !c.with_hyper ? lean_check(cfg)
                         : kind != SCONE_LEAN_SGD && kind != SCONE_LEAN_ROWWISE_ADAGRAD              ? "bad kind"
                         : rounding != SCONE_ROUND_NEAREST && rounding != SCONE_ROUND_STOCHASTIC ? "bad rounding"
                                                                                                 : nullptr;
-  SCONE_TRY(opt_need_table(h, who, bad_cfg));
-  if (with_ctl && !d_ctl) return scone_refuse(h, SCONE_EINVAL, who, "null d_ctl");
-  if (with_n && !d_n) return scone_refuse(h, SCONE_EINVAL, who, "null d_n");
-  if (with_hyper && !d_hyper) return scone_refuse(h, SCONE_EINVAL, who, "null d_hyper");
+  SCONE_TRY(opt_open(h, c, bad_cfg));
   const int fmt = h->cfg.table_fmt;
   const bool inplace = d_master == nullptr, stoch = rounding == SCONE_ROUND_STOCHASTIC;
-  if (inplace && fmt != SCONE_FMT_F32 && fmt != SCONE_FMT_BF16)
-    return scone_refuse(h, SCONE_EINVAL, who,
-                        (std::string("in place (d_master == NULL) needs an fp32 or bf16 table, this one is ") + scone_fmt_name(fmt)).c_str());
-  if (stoch && !inplace)
-    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding with a master: there is nothing to round");
-  if (stoch && fmt != SCONE_FMT_BF16)
-    return scone_refuse(h, SCONE_EINVAL, who, "stochastic rounding on an fp32 table: there is nothing to round");
+  SCONE_TRY(lean_inplace_check(h, c.who, stoch, !inplace, true));
   if (n == 0) return SCONE_OK;
-  if (!d_row_ids || !d_grad_rows) return scone_refuse(h, SCONE_EINVAL, who, "null pointer");
+  if (!d_row_ids || !d_grad_rows) return scone_refuse(h, SCONE_EINVAL, c.who, "null pointer");
   if (kind == SCONE_LEAN_ROWWISE_ADAGRAD && !d_row_state)
-    return scone_refuse(h, SCONE_EINVAL, who, "row-wise Adagrad needs d_row_state (one fp32 per owned row)");
+    return scone_refuse(h, SCONE_EINVAL, c.who, "row-wise Adagrad needs d_row_state (one fp32 per owned row)");
   SCONE_ON_DEVICE(h);
   lean_args a;
-  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state, a.ctl = d_ctl;
-  a.d_n = reinterpret_cast<const unsigned long long *>(d_n);
-  a.hyper = d_hyper;
+  a.ids = d_row_ids, a.grad = d_grad_rows, a.n = n, a.master = d_master, a.row_state = d_row_state;
   a.rnd = lean_rand{0, 0}, a.sc = scone_opt_scalars{};
-  if (!with_hyper) {
+  if (!c.with_hyper) {
     a.rnd.seed = cfg->seed, a.rnd.step = cfg->step;
     lean_scalars(cfg, &a.sc);
   }
@@ -238,13 +213,13 @@ int opt_step_lean(scone_handle *h, const char *who, const scone_lean_cfg *cfg, c
   hipStream_t s = (hipStream_t)stream;
   if (inplace) {
     if (fmt == SCONE_FMT_F32)
-      lean_launch_kind<SCONE_FMT_F32, true, false>(h, kind, a, blocks, s);
+      lean_launch<SCONE_FMT_F32, true, false>(h, kind, c, a, blocks, s);
     else if (stoch)
-      lean_launch_kind<SCONE_FMT_BF16, true, true>(h, kind, a, blocks, s);
+      lean_launch<SCONE_FMT_BF16, true, true>(h, kind, c, a, blocks, s);
     else
-      lean_launch_kind<SCONE_FMT_BF16, true, false>(h, kind, a, blocks, s);
-  } else if (scone_dispatch_fmt(fmt, [&](auto F) { lean_launch_kind<decltype(F)::value, false, false>(h, kind, a, blocks, s); })) {
-    return scone_refuse(h, SCONE_EINVAL, who, "bad format");
+      lean_launch<SCONE_FMT_BF16, true, false>(h, kind, c, a, blocks, s);
+  } else if (scone_dispatch_fmt(fmt, [&](auto F) { lean_launch<decltype(F)::value, false, false>(h, kind, c, a, blocks, s); })) {
+    return scone_refuse(h, SCONE_EINVAL, c.who, "bad format");
   }
   SCONE_HIP(h, hipGetLastError());
   return SCONE_OK;
@@ -254,25 +229,27 @@ int opt_step_lean(scone_handle *h, const char *who, const scone_lean_cfg *cfg, c
 
 extern "C" int scone_opt_step_lean(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                                    uint64_t n, float *d_master, float *d_row_state, scone_stream_t stream) {
-  return opt_step_lean(h, "scone_opt_step_lean", cfg, d_row_ids, d_grad_rows, n, d_master, d_row_state, false, nullptr, stream);
+  return opt_step_lean(h, {.who = "scone_opt_step_lean"}, cfg, d_row_ids, d_grad_rows, n, d_master, d_row_state, stream);
 }
 
 extern "C" int scone_opt_step_lean_ctl(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                                        uint64_t n, float *d_master, float *d_row_state, const scone_grad_ctl *d_ctl,
                                        scone_stream_t stream) {
-  return opt_step_lean(h, "scone_opt_step_lean_ctl", cfg, d_row_ids, d_grad_rows, n, d_master, d_row_state, true, d_ctl, stream);
+  return opt_step_lean(h, {.who = "scone_opt_step_lean_ctl", .d_ctl = d_ctl, .need_ctl = true}, cfg, d_row_ids, d_grad_rows, n, d_master,
+                       d_row_state, stream);
 }
 
 extern "C" int scone_opt_step_lean_dn(scone_handle *h, const scone_lean_cfg *cfg, const int64_t *d_row_ids, const float *d_grad_rows,
                                       const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_row_state,
                                       const scone_grad_ctl *d_ctl, scone_stream_t stream) {
-  return opt_step_lean(h, "scone_opt_step_lean_dn", cfg, d_row_ids, d_grad_rows, n_cap, d_master, d_row_state, false, d_ctl, stream, true,
-                       d_n);
+  return opt_step_lean(h, {.who = "scone_opt_step_lean_dn", .d_ctl = d_ctl, .d_n = d_n, .with_n = true}, cfg, d_row_ids, d_grad_rows, n_cap,
+                       d_master, d_row_state, stream);
 }
 
 extern "C" int scone_opt_step_lean_dh(scone_handle *h, int32_t kind, int32_t rounding, const int64_t *d_row_ids, const float *d_grad_rows,
                                       const uint64_t *d_n, uint64_t n_cap, float *d_master, float *d_row_state,
                                       const scone_opt_hyper *d_hyper, const scone_grad_ctl *d_ctl, void *stream) {
-  return opt_step_lean(h, "scone_opt_step_lean_dh", nullptr, d_row_ids, d_grad_rows, n_cap, d_master, d_row_state, false, d_ctl, stream,
-                       true, d_n, true, kind, rounding, d_hyper);
+  return opt_step_lean(h, {.who = "scone_opt_step_lean_dh", .d_ctl = d_ctl, .d_n = d_n, .with_n = true, .d_hyper = d_hyper,
+                           .with_hyper = true, .kind = kind, .rounding = rounding},
+                       nullptr, d_row_ids, d_grad_rows, n_cap, d_master, d_row_state, stream);
 }

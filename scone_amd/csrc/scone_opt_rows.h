@@ -37,6 +37,27 @@ static inline const char *opt_cfg_check(const scone_opt_cfg *cfg, bool adam_need
   if (adam_needs_step && cfg->kind == SCONE_OPT_ADAM && cfg->step < 1) return "Adam needs step >= 1";
   return nullptr;
 }
+// Which form of a step this is: what the by-value, _ctl, _dn and _dh entry points of both steps differ in.  The extern "C"
+// wrappers fill it by designated fields; what a form does not have stays null / false.
+struct opt_call {
+  const char *who;                          // the entry point's name, for its refusals
+  const scone_grad_ctl *d_ctl = nullptr;    // the control block; the kernel reads it when it is not null
+  bool need_ctl = false;                    // _ctl: a null d_ctl is refused (beside a device count the block is optional)
+  const uint64_t *d_n = nullptr;            // _dn, _dh: the count on the device, the call's n its cap
+  bool with_n = false;
+  const scone_opt_hyper *d_hyper = nullptr;  // _dh: the scalars on the device; the cfg is null and ...
+  bool with_hyper = false;
+  int32_t kind = 0, rounding = 0;           // ... these come by value in its place (rounding: the lean step's)
+};
+// the refusals every form of both steps opens with, in this order (bad_cfg: the unit's verdict on its cfg, or on the kind and
+// rounding of a _dh call); the unit's own checks, the n == 0 early success and the data pointers follow
+static inline int opt_open(scone_handle *h, const opt_call &c, const char *bad_cfg) {
+  SCONE_TRY(opt_need_table(h, c.who, bad_cfg));
+  if (c.need_ctl && !c.d_ctl) return scone_refuse(h, SCONE_EINVAL, c.who, "null d_ctl");
+  if (c.with_n && !c.d_n) return scone_refuse(h, SCONE_EINVAL, c.who, "null d_n");
+  if (c.with_hyper && !c.d_hyper) return scone_refuse(h, SCONE_EINVAL, c.who, "null d_hyper");
+  return SCONE_OK;
+}
 // the table is about to change: as scone_table_store_f32_ids, the staged cache of cold rows is dropped.  Returns the grid for n
 // listed rows, a wave each (SCONE_OPT_MAX_BLOCKS caps it)
 static inline unsigned opt_begin(scone_handle *h, unsigned long long n) {
@@ -90,6 +111,20 @@ struct opt_s_device {
     r.step = hy->step;
   }
 };
+
+// The sources of a call (host side): launch(nsrc, ssrc) is called once, with the pair the form has -- count and scalars by value,
+// the count on the device, or both on the device.  These three are every combination the kernels are instantiated for: there is
+// no form with a by-value count beside scalars on the device.
+template <typename F>
+static inline void opt_with_sources(const opt_call &c, unsigned long long n, const scone_opt_scalars &sc, F &&launch) {
+  const unsigned long long *d_n = reinterpret_cast<const unsigned long long *>(c.d_n);
+  if (c.with_hyper)
+    launch(opt_n_device{d_n, n}, opt_s_device{c.d_hyper});
+  else if (c.with_n)
+    launch(opt_n_device{d_n, n}, opt_s_value{sc});
+  else
+    launch(opt_n_value{n}, opt_s_value{sc});
+}
 
 // a wave-uniform float computed by the vector unit, put back where a kernel argument lives (a scalar register): the kernels read
 // gscale in every element's statement, and the _ctl entry points replace it by a product

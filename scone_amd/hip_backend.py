@@ -403,6 +403,27 @@ def _no_scalars_beside_hyper(who: str, given: dict) -> None:
                          "would be ignored -- write the block instead (hyper.lr.fill_(...), hyper.grad_scale.copy_(...))")
 
 
+# the by-value scalars of the two steps: (their defaults -- lr has none --, what a cfg that carries only the kind holds beside hyper=)
+_OPT_SCALARS = (dict(lr=None, step=1, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0),
+                dict(lr=0.0, step=1, betas=(0.0, 0.0), eps=0.0, weight_decay=0.0, grad_scale=1.0))
+_LEAN_SCALARS = (dict(lr=None, eps=1e-10, weight_decay=0.0, grad_scale=1.0, seed=0, step=1),
+                 dict(lr=0.0, eps=0.0, weight_decay=0.0, grad_scale=1.0, seed=0, step=1))
+
+
+def _step_scalars(who: str, scalars, given: dict, n=None, hyper=None) -> dict:
+    """The by-value scalars of a step, ``None`` replaced by the default -- or, with ``hyper=`` (which needs ``n=`` and takes no
+    scalar beside it), the placeholders of a cfg that is read for its kind only."""
+    defaults, kind_only = scalars
+    if hyper is not None:
+        _no_scalars_beside_hyper(who, given)
+        if n is None:
+            raise ValueError(f"{who}: hyper= needs n= (a 1-element int64 device tensor that holds the row count)")
+        return kind_only
+    if given["lr"] is None:
+        raise ValueError(f"{who}: lr is required (or hyper=)")
+    return {name: defaults[name] if v is None else v for name, v in given.items()}
+
+
 class OptHyper:
     """``scone_opt_hyper``: the 104 device bytes that hold an optimizer's hyper-parameters and its step count
     (include/scone_hip.h, "optimizer hyper-parameters on the device"); :meth:`SconeTable.opt_hyper` makes one.  ``lr``,
@@ -607,18 +628,13 @@ class BackwardPlan:
         arguments are those two calls'.  Stream-ordered, at most two kernel launches, no allocation.  A table wider than
         ``APPLY_LEAN_MAX_DIM`` takes the two calls (the library does not fuse it).  Returns ``n_rows``."""
         plan, t = self._plan(), self._table
-        cfg = _lean_cfg(kind, lr, eps, weight_decay, grad_scale, rounding, seed, step)
+        cfg = _lean_cfg(kind, rounding=rounding, **_step_scalars("apply_lean", _LEAN_SCALARS, dict(
+            lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, seed=seed, step=step)))
         if t.fmt not in (L.FMT_F32, L.FMT_BF16):
             raise ValueError(f"apply_lean: in place needs an fp32 or bf16 table, this one has format code {t.fmt}")
         if cfg.rounding == L.ROUND_STOCHASTIC and t.fmt != L.FMT_BF16:
             raise ValueError("apply_lean: stochastic rounding is for bf16 rows (on an fp32 table there is nothing to round)")
-        owned = t.row_end - t.row_begin
-        if row_state is None:
-            if cfg.kind == L.LEAN_ROWWISE_ADAGRAD:
-                raise ValueError("apply_lean: this kind needs row_state")
-        elif not (isinstance(row_state, torch.Tensor) and row_state.dtype == torch.float32 and tuple(row_state.shape) == (owned,)
-                  and row_state.device == t.device and row_state.is_contiguous()):
-            raise ValueError(f"apply_lean: row_state must be a contiguous fp32 [{owned}] tensor on {t.device} (it is updated in place)")
+        t._state_operand("apply_lean", "row_state", row_state, (t.row_end - t.row_begin,), cfg.kind == L.LEAN_ROWWISE_ADAGRAD)
         if grad_out.dtype not in _DT:
             raise ValueError(f"grad_out must be fp32, fp16 or bf16, not {grad_out.dtype}")
         if grad_out.numel() != self.ntok * t.dim or (grad_out.dim() and grad_out.shape[-1] != t.dim and grad_out.numel()):
@@ -1357,6 +1373,53 @@ class SconeTable:
             raise ValueError(f"{who}: rows must be fp32 [{ids.shape[0]}, {self.dim}], got {rows.dtype} {tuple(rows.shape)}")
         return ids.to(device=self.device).contiguous(), rows.to(device=self.device).contiguous()
 
+    def _step_operands(self, who: str, row_ids: torch.Tensor, grad_rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(row_ids, grad_rows)`` of an optimizer step: :meth:`_sparse_operand`'s conditions, refused in the steps' own words."""
+        if row_ids.dim() != 1 or grad_rows.dim() != 2 or grad_rows.shape[0] != row_ids.numel() or grad_rows.shape[1] != self.dim:
+            raise ValueError(f"{who}: row_ids [U] and grad_rows [U, {self.dim}], got {tuple(row_ids.shape)} and "
+                             f"{tuple(grad_rows.shape)}")
+        if row_ids.dtype != torch.int64 or grad_rows.dtype != torch.float32:
+            raise ValueError(f"{who}: row_ids must be int64 and grad_rows fp32")
+        return row_ids.to(device=self.device).contiguous(), grad_rows.to(device=self.device).contiguous()
+
+    def _state_operand(self, who: str, name: str, t: Optional[torch.Tensor], shape: tuple, needed: bool) -> None:
+        """A master or state tensor of an optimizer step: absent only if the kind does not need it, else contiguous fp32 of
+        ``shape`` on the table's device (it is updated in place, so it is never copied or moved)."""
+        if t is None:
+            if needed:
+                raise ValueError(f"{who}: this kind needs {name}")
+        elif not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == self.device
+                  and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 {list(shape)} tensor on {self.device} (it is updated in place)")
+
+    def _step_call(self, base: str, cfg, dh_prefix: tuple, row_ids: torch.Tensor, grad_rows: torch.Tensor, states: tuple,
+                   ctl: Optional["GradCtl"], n: Optional[torch.Tensor], hyper: Optional[OptHyper]) -> None:
+        """One optimizer step through the form of ``base`` (``scone_opt_step`` / ``scone_opt_step_lean``) that ``(ctl, n, hyper)``
+        select: ``_dh`` with ``hyper`` (``dh_prefix``, the kind -- and rounding -- by value, stands where the others take the cfg),
+        ``_dn`` with ``n``, ``_ctl`` with ``ctl`` alone, else the plain call.  ``states``: the master and state tensors, in the
+        entry point's order.  The operands are recorded on the stream (they may be temporaries of the caller) in the forms without
+        ``n``; with ``n`` they are buffers the caller keeps across steps."""
+        U = row_ids.numel()
+        if n is not None:
+            n = _device_count(base[len("scone_"):], n, self.device)
+        head = dh_prefix if hyper is not None else (C.byref(cfg),)
+        rows = (_ptr(row_ids), _ptr(grad_rows), *(() if n is None else (_ptr(n),)), U, *(_ptr(t) for t in states))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            if hyper is not None:
+                name, tail = base + "_dh", (_ptr(hyper.buf), None if ctl is None else _ptr(ctl.buf))
+            elif n is not None:
+                name, tail = base + "_dn", (None if ctl is None else _ptr(ctl.buf),)
+            elif ctl is not None:
+                name, tail = base + "_ctl", (_ptr(ctl.buf),)
+            else:
+                name, tail = base, ()
+            rc = getattr(L.lib(), name)(self._h, *head, *rows, *tail, stream.cuda_stream)
+        self._check(rc, name)
+        if n is None and U:
+            row_ids.record_stream(stream)
+            grad_rows.record_stream(stream)
+
     def grad_merge_map(self, ids_a: torch.Tensor, ids_b: torch.Tensor, sync: bool = True) -> GradMergeMap:
         """``scone_grad_merge_map``: the union of two ascending lists of distinct int64 row ids and the maps between the three
         row numberings (include/scone_hip.h, "gradient accumulation"), a :class:`GradMergeMap`.  ``sync=True`` synchronises
@@ -1561,62 +1624,14 @@ class SconeTable:
         :meth:`opt_hyper_advance` left in the block, read on the device; the step changes nothing if that advance did not apply.
         ``lr`` (required without ``hyper``), ``step`` (1), ``betas`` ((0.9, 0.999)), ``eps`` (1e-8), ``weight_decay`` (0) and
         ``grad_scale`` (1) are the by-value scalars: any of them beside ``hyper=`` is a ``ValueError``."""
-        if hyper is not None:
-            _no_scalars_beside_hyper("opt_step", dict(lr=lr, step=step, betas=betas, eps=eps, weight_decay=weight_decay,
-                                                      grad_scale=grad_scale))
-            if n is None:
-                raise ValueError("opt_step: hyper= needs n= (a 1-element int64 device tensor that holds the row count)")
-            cfg = _opt_cfg(kind, 0.0, (0.0, 0.0), 0.0, 0.0, 1.0, 1)        # the kind only
-        else:
-            if lr is None:
-                raise ValueError("opt_step: lr is required (or hyper=)")
-            cfg = _opt_cfg(kind, lr, (0.9, 0.999) if betas is None else betas, 1e-8 if eps is None else eps,
-                           0.0 if weight_decay is None else weight_decay, 1.0 if grad_scale is None else grad_scale,
-                           1 if step is None else step)
-        owned = self.row_end - self.row_begin
-        for name, t, needed in (("master", master, True), ("state1", state1, cfg.kind == L.OPT_ADAM),
-                                ("state2", state2, cfg.kind in (L.OPT_ADAM, L.OPT_ADAGRAD))):
-            if t is None:
-                if needed:
-                    raise ValueError(f"opt_step: this kind needs {name}")
-                continue
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (owned, self.dim)
-                    and t.device == self.device and t.is_contiguous()):
-                raise ValueError(f"opt_step: {name} must be a contiguous fp32 [{owned}, {self.dim}] tensor on {self.device} "
-                                 "(it is updated in place)")
-        if row_ids.dim() != 1 or grad_rows.dim() != 2 or grad_rows.shape[0] != row_ids.numel() or grad_rows.shape[1] != self.dim:
-            raise ValueError(f"opt_step: row_ids [U] and grad_rows [U, {self.dim}], got {tuple(row_ids.shape)} and "
-                             f"{tuple(grad_rows.shape)}")
-        if row_ids.dtype != torch.int64 or grad_rows.dtype != torch.float32:
-            raise ValueError("opt_step: row_ids must be int64 and grad_rows fp32")
-        row_ids = row_ids.to(device=self.device).contiguous()
-        grad_rows = grad_rows.to(device=self.device).contiguous()
-        if n is not None:
-            n = _device_count("opt_step", n, self.device)
-            with torch.cuda.device(self.device):
-                if hyper is not None:
-                    rc = L.lib().scone_opt_step_dh(self._h, cfg.kind, _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
-                                                   _ptr(master), _ptr(state1), _ptr(state2), _ptr(hyper.buf),
-                                                   None if ctl is None else _ptr(ctl.buf),
-                                                   torch.cuda.current_stream(self.device).cuda_stream)
-                else:
-                    rc = L.lib().scone_opt_step_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
-                                                   _ptr(master), _ptr(state1), _ptr(state2), None if ctl is None else _ptr(ctl.buf),
-                                                   torch.cuda.current_stream(self.device).cuda_stream)
-            self._check(rc, "scone_opt_step_dn" if hyper is None else "scone_opt_step_dh")
-            return
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device)
-            if ctl is None:
-                rc = L.lib().scone_opt_step(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
-                                            _ptr(state1), _ptr(state2), stream.cuda_stream)
-            else:
-                rc = L.lib().scone_opt_step_ctl(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(),
-                                                _ptr(master), _ptr(state1), _ptr(state2), _ptr(ctl.buf), stream.cuda_stream)
-        self._check(rc, "scone_opt_step" if ctl is None else "scone_opt_step_ctl")
-        if row_ids.numel():                                        # they may be temporaries of the caller
-            row_ids.record_stream(stream)
-            grad_rows.record_stream(stream)
+        cfg = _opt_cfg(kind, **_step_scalars("opt_step", _OPT_SCALARS, dict(
+            lr=lr, step=step, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale), n, hyper))
+        shape = (self.row_end - self.row_begin, self.dim)
+        self._state_operand("opt_step", "master", master, shape, True)
+        self._state_operand("opt_step", "state1", state1, shape, cfg.kind == L.OPT_ADAM)
+        self._state_operand("opt_step", "state2", state2, shape, cfg.kind in (L.OPT_ADAM, L.OPT_ADAGRAD))
+        row_ids, grad_rows = self._step_operands("opt_step", row_ids, grad_rows)
+        self._step_call("scone_opt_step", cfg, (cfg.kind,), row_ids, grad_rows, (master, state1, state2), ctl, n, hyper)
 
     def opt_step_lean(self, row_ids: torch.Tensor, grad_rows: torch.Tensor, *, kind, lr: Optional[float] = None,
                       master: Optional[torch.Tensor] = None, row_state: Optional[torch.Tensor] = None, eps: Optional[float] = None,
@@ -1635,18 +1650,8 @@ class SconeTable:
         random bits' ``seed`` and ``step``, are read from the block on the device, as for :meth:`opt_step`.  ``lr`` (required
         without ``hyper``), ``eps`` (1e-10), ``weight_decay`` (0), ``grad_scale`` (1), ``seed`` (0) and ``step`` (1) are the by-value
         scalars: any of them beside ``hyper=`` is a ``ValueError``."""
-        if hyper is not None:
-            _no_scalars_beside_hyper("opt_step_lean", dict(lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, seed=seed,
-                                                           step=step))
-            if n is None:
-                raise ValueError("opt_step_lean: hyper= needs n= (a 1-element int64 device tensor that holds the row count)")
-            cfg = _lean_cfg(kind, 0.0, 0.0, 0.0, 1.0, rounding, 0, 1)       # kind and rounding only
-        else:
-            if lr is None:
-                raise ValueError("opt_step_lean: lr is required (or hyper=)")
-            cfg = _lean_cfg(kind, lr, 1e-10 if eps is None else eps, 0.0 if weight_decay is None else weight_decay,
-                            1.0 if grad_scale is None else grad_scale, rounding, 0 if seed is None else seed,
-                            1 if step is None else step)
+        cfg = _lean_cfg(kind, rounding=rounding, **_step_scalars("opt_step_lean", _LEAN_SCALARS, dict(
+            lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, seed=seed, step=step), n, hyper))
         owned = self.row_end - self.row_begin
         if master is None and self.fmt not in (L.FMT_F32, L.FMT_BF16):
             raise ValueError("opt_step_lean: in place (master=None) needs an fp32 or bf16 table, this one has format code "
@@ -1654,49 +1659,10 @@ class SconeTable:
         if cfg.rounding == L.ROUND_STOCHASTIC and (master is not None or self.fmt != L.FMT_BF16):
             raise ValueError("opt_step_lean: stochastic rounding is for in-place bf16 rows (with a master or on an fp32 table "
                              "there is nothing to round)")
-        for name, t, shape, needed in (("master", master, (owned, self.dim), False),
-                                       ("row_state", row_state, (owned,), cfg.kind == L.LEAN_ROWWISE_ADAGRAD)):
-            if t is None:
-                if needed:
-                    raise ValueError(f"opt_step_lean: this kind needs {name}")
-                continue
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape
-                    and t.device == self.device and t.is_contiguous()):
-                raise ValueError(f"opt_step_lean: {name} must be a contiguous fp32 {list(shape)} tensor on {self.device} "
-                                 "(it is updated in place)")
-        if row_ids.dim() != 1 or grad_rows.dim() != 2 or grad_rows.shape[0] != row_ids.numel() or grad_rows.shape[1] != self.dim:
-            raise ValueError(f"opt_step_lean: row_ids [U] and grad_rows [U, {self.dim}], got {tuple(row_ids.shape)} and "
-                             f"{tuple(grad_rows.shape)}")
-        if row_ids.dtype != torch.int64 or grad_rows.dtype != torch.float32:
-            raise ValueError("opt_step_lean: row_ids must be int64 and grad_rows fp32")
-        row_ids = row_ids.to(device=self.device).contiguous()
-        grad_rows = grad_rows.to(device=self.device).contiguous()
-        if n is not None:
-            n = _device_count("opt_step_lean", n, self.device)
-            with torch.cuda.device(self.device):
-                if hyper is not None:
-                    rc = L.lib().scone_opt_step_lean_dh(self._h, cfg.kind, cfg.rounding, _ptr(row_ids), _ptr(grad_rows), _ptr(n),
-                                                        row_ids.numel(), _ptr(master), _ptr(row_state), _ptr(hyper.buf),
-                                                        None if ctl is None else _ptr(ctl.buf),
-                                                        torch.cuda.current_stream(self.device).cuda_stream)
-                else:
-                    rc = L.lib().scone_opt_step_lean_dn(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), _ptr(n), row_ids.numel(),
-                                                        _ptr(master), _ptr(row_state), None if ctl is None else _ptr(ctl.buf),
-                                                        torch.cuda.current_stream(self.device).cuda_stream)
-            self._check(rc, "scone_opt_step_lean_dn" if hyper is None else "scone_opt_step_lean_dh")
-            return
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device)
-            if ctl is None:
-                rc = L.lib().scone_opt_step_lean(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(), _ptr(master),
-                                                 _ptr(row_state), stream.cuda_stream)
-            else:
-                rc = L.lib().scone_opt_step_lean_ctl(self._h, C.byref(cfg), _ptr(row_ids), _ptr(grad_rows), row_ids.numel(),
-                                                     _ptr(master), _ptr(row_state), _ptr(ctl.buf), stream.cuda_stream)
-        self._check(rc, "scone_opt_step_lean" if ctl is None else "scone_opt_step_lean_ctl")
-        if row_ids.numel():                                        # they may be temporaries of the caller
-            row_ids.record_stream(stream)
-            grad_rows.record_stream(stream)
+        self._state_operand("opt_step_lean", "master", master, (owned, self.dim), False)
+        self._state_operand("opt_step_lean", "row_state", row_state, (owned,), cfg.kind == L.LEAN_ROWWISE_ADAGRAD)
+        row_ids, grad_rows = self._step_operands("opt_step_lean", row_ids, grad_rows)
+        self._step_call("scone_opt_step_lean", cfg, (cfg.kind, cfg.rounding), row_ids, grad_rows, (master, row_state), ctl, n, hyper)
 
     def embed_prefetch(self, tok: torch.Tensor, tokens_ready: bool = False) -> None:
         """``scone_embed_prefetch``: start the pinned-host prefetch pipeline for ``tok`` (int32 ``[B, T]`` on the device: pass the

@@ -505,124 +505,57 @@ class FGramOptimizer:
             return True
         return (self.kind != "adam" or self.state1 is not None) and (self.kind == "sgd" or self.state2 is not None)
 
-    def _step_static(self, static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite) -> int:
-        """``step()`` on the triple of a static backward: the ``_dn`` calls, which read the row count on the device."""
-        ids, rows, n = static
-        module = self.module
-        table = module.cache.to_device()
-        if torch.cuda.is_current_stream_capturing():
-            # the step-dependent scalars are launch arguments: a replayed graph would repeat them as captured
-            if self.kind == "adam":
-                raise ValueError("FGramOptimizer.step under capture: Adam's bias correction depends on the step count, which a "
-                                 "replayed graph would repeat as captured; use sgd, adagrad or rowwise_adagrad, or step eagerly")
-            if self.rounding == "stochastic":
-                raise ValueError("FGramOptimizer.step under capture: stochastic rounding draws its bits from the step count, which "
-                                 "a replayed graph would repeat as captured; use rounding='nearest', or step eagerly")
-            if not self._static_state_ready() or (ctl_road and self._static_ctl is None):
-                raise ValueError("FGramOptimizer.step under capture: the optimizer state is allocated at the first step; run one "
-                                 "step eagerly (the warm-up) before capturing")
-        lo, hi = table.row_begin, table.row_end
-        ctl = None
-        if ctl_road:
-            if self._static_ctl is None:
-                from scone_amd.hip_backend import GradCtl
-                self._static_ctl = GradCtl(table.device)
-                self._static_sq = torch.zeros((), dtype=torch.float64, device=table.device)
-                self._static_scratch = torch.zeros(_lib.grad_sqnorm_scratch(rows.shape[0]), dtype=torch.float64, device=table.device)
-            extra = [] if extra_sqnorm is None else (list(extra_sqnorm) if isinstance(extra_sqnorm, (list, tuple)) else [extra_sqnorm])
-            sq = table.grad_sqnorm(rows, self._static_scratch, n=n, out=self._static_sq)[0]
-            ctl = table.grad_ctl([sq, *extra], grad_scale=grad_scale, max_norm=max_norm, skip_nonfinite=skip_nonfinite,
-                                 out=self._static_ctl)
-            self.last_ctl = ctl
-        self.t += 1
-        self._ensure_state()
-
-        def own(x):
-            return None if x is None else x[lo:hi]
-
-        if self.in_place:
-            table.opt_step_lean(ids, rows, kind=self.kind, lr=self.lr, row_state=own(self.state2), eps=self.eps,
-                                weight_decay=self.weight_decay, grad_scale=grad_scale, rounding=self.rounding, seed=self.seed,
-                                step=self.t, ctl=ctl, n=n)
-        elif self.kind == "rowwise_adagrad":
-            table.opt_step_lean(ids, rows, kind=self.kind, lr=self.lr, master=own(module.weight.detach()),
-                                row_state=own(self.state2), eps=self.eps, weight_decay=self.weight_decay, grad_scale=grad_scale,
-                                step=self.t, ctl=ctl, n=n)
-        else:
-            table.opt_step(ids, rows, own(module.weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
-                           state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
-                           grad_scale=grad_scale, ctl=ctl, n=n)
-        if not self.in_place:
-            module._touched = []                         # the served table is current: commit() has nothing to store
-        return int(ids.numel())
-
-    def _step_hyper(self, static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite) -> int:
-        """``step()`` with ``capturable=True``: ``grad_ctl(hyper=)``, ``opt_hyper_advance``, then the ``_dh`` step -- every scalar
-        is read on the device.  ``static``: the triple of a static backward, or ``None`` (the gradient on the module; its row count
-        goes into a device word the optimizer keeps)."""
-        module = self.module
-        table = module.cache.to_device()
-        capturing = torch.cuda.is_current_stream_capturing()
-        if static is not None:
-            ids, rows, n = static
-        else:
-            if capturing:
-                raise ValueError("FGramOptimizer.step under capture needs a module built with static_rows= (the default backward "
-                                 "synchronises)")
-            grad = self._current_grad()
-            if grad is None:
-                return 0
-            ids, rows = grad
-            ids, rows = ids.contiguous(), rows.contiguous()
-            n = self._n_word.fill_(ids.numel())
-        if capturing and (not self._static_state_ready() or (ctl_road and self._static_ctl is None)):
+    def _need_warm_up(self, ctl_road: bool) -> None:
+        """Under capture nothing may be allocated: the state, and on the clipped road the kept control buffers, must be there."""
+        if not self._static_state_ready() or (ctl_road and self._static_ctl is None):
             raise ValueError("FGramOptimizer.step under capture: the optimizer state is allocated at the first step; run one "
                              "step eagerly (the warm-up) before capturing")
-        if isinstance(grad_scale, torch.Tensor):
-            if grad_scale.dtype != torch.float64 or grad_scale.numel() != 1 or grad_scale.device != table.device:
-                raise ValueError(f"FGramOptimizer.step: a grad_scale on the device must be one float64 on {table.device}")
-            self.hyper.grad_scale.copy_(grad_scale.reshape(()))
-        elif grad_scale is not None:
-            self.hyper.grad_scale.fill_(float(grad_scale))
-        ctl = None
-        if ctl_road:
+
+    def _static_control(self, table, cap: int):
+        """Static mode's control block, squared norm and norm scratch (for buffers of ``cap`` rows): allocated at the first
+        clipped step, then kept across steps -- and replays."""
+        if self._static_ctl is None:
             from scone_amd.hip_backend import GradCtl
-            extra = [] if extra_sqnorm is None else (list(extra_sqnorm) if isinstance(extra_sqnorm, (list, tuple)) else [extra_sqnorm])
-            if static is not None:
-                if self._static_ctl is None:
-                    self._static_ctl = GradCtl(table.device)
-                    self._static_sq = torch.zeros((), dtype=torch.float64, device=table.device)
-                    self._static_scratch = torch.zeros(_lib.grad_sqnorm_scratch(rows.shape[0]), dtype=torch.float64,
-                                                       device=table.device)
-                sq = table.grad_sqnorm(rows, self._static_scratch, n=n, out=self._static_sq)[0]
-                out = self._static_ctl
-            else:
-                sq, out = table.grad_sqnorm(rows)[0], None
-            ctl = table.grad_ctl([sq, *extra], max_norm=max_norm, skip_nonfinite=skip_nonfinite, out=out, hyper=self.hyper)
-            self.last_ctl = ctl
-        table.opt_hyper_advance(self.hyper, self.kind, ctl)
-        self._ensure_state()
+            self._static_ctl = GradCtl(table.device)
+            self._static_sq = torch.zeros((), dtype=torch.float64, device=table.device)
+            self._static_scratch = torch.zeros(_lib.grad_sqnorm_scratch(cap), dtype=torch.float64, device=table.device)
+        return self._static_ctl, self._static_sq, self._static_scratch
+
+    @staticmethod
+    def _extra_terms(extra_sqnorm) -> list:
+        """``extra_sqnorm`` -- nothing, one term or a sequence of terms -- as a list."""
+        if extra_sqnorm is None:
+            return []
+        return list(extra_sqnorm) if isinstance(extra_sqnorm, (list, tuple)) else [extra_sqnorm]
+
+    def _launch_step(self, ids, rows, *, grad_scale, ctl, n=None, hyper=None) -> None:
+        """The one launch of every road: ``opt_step_lean`` in place on the served rows, ``opt_step_lean`` on the master for
+        row-wise Adagrad, else ``opt_step``.  ``n`` / ``hyper``: the row count / the scalars on the device; without ``hyper`` the
+        scalars go by value, ``self.t`` (already advanced) among them."""
+        module = self.module
+        table = module.cache.to_device()
         lo, hi = table.row_begin, table.row_end
 
-        def own(x):
+        def own(x):                                      # the rows this handle owns: a contiguous view
             return None if x is None else x[lo:hi]
 
+        scalars = {} if hyper is not None else dict(lr=self.lr, eps=self.eps, weight_decay=self.weight_decay,
+                                                    grad_scale=grad_scale, step=self.t)
         if self.in_place:
+            if hyper is None:
+                scalars["seed"] = self.seed
             table.opt_step_lean(ids, rows, kind=self.kind, row_state=own(self.state2), rounding=self.rounding, ctl=ctl, n=n,
-                                hyper=self.hyper)
-        elif self.kind == "rowwise_adagrad":
+                                hyper=hyper, **scalars)
+            return
+        if self.kind == "rowwise_adagrad":
             table.opt_step_lean(ids, rows, kind=self.kind, master=own(module.weight.detach()), row_state=own(self.state2), ctl=ctl,
-                                n=n, hyper=self.hyper)
+                                n=n, hyper=hyper, **scalars)
         else:
+            if hyper is None:
+                scalars["betas"] = self.betas
             table.opt_step(ids, rows, own(module.weight.detach()), kind=self.kind, state1=own(self.state1), state2=own(self.state2),
-                           ctl=ctl, n=n, hyper=self.hyper)
-        if static is None:
-            stream = torch.cuda.current_stream(table.device)
-            ids.record_stream(stream)                    # they may be temporaries of the caller
-            rows.record_stream(stream)
-        if not self.in_place:
-            module._touched = []                         # the served table is current: commit() has nothing to store
-        return int(ids.numel())
+                           ctl=ctl, n=n, hyper=hyper, **scalars)
+        module._touched = []                             # the served table is current: commit() has nothing to store
 
     def found_nonfinite(self) -> bool:
         """Whether the last ``step(...)`` that took a clipping / skipping argument found inf or NaN and skipped (with
@@ -660,58 +593,71 @@ class FGramOptimizer:
         Eagerly both work; with ``capturable=True`` both are captured.  A backward that overflowed ``static_rows`` left
         ``n = 0``: the step changes nothing (:meth:`rows_overflowed`)."""
         ctl_road = max_norm is not None or extra_sqnorm is not None or bool(skip_nonfinite)
-        static = getattr(self.module, "static_grad", None)
-        if self.capturable:
-            return self._step_hyper(static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite)
-        if static is not None:
-            return self._step_static(static, grad_scale, ctl_road, max_norm, extra_sqnorm, skip_nonfinite)
-        if self.fused_backward:
+        if self.fused_backward:                          # (never capturable, never a static module: _set_fused)
             if ctl_road:
                 raise ValueError("FGramOptimizer.step: max_norm / extra_sqnorm / skip_nonfinite need the gradient's norm before the "
                                  "first row is written, and fused_backward=True has updated the rows in the backward; use the "
                                  "default road (fused_backward=False)")
             n, self._fused_rows = self._fused_rows, 0    # the backwards have updated the rows already
             return n
-        grad = self._current_grad()
-        if grad is None:
-            return 0
-        row_ids, grad_rows = grad
-        module = self.module
-        table = module.cache.to_device()
-        lo, hi = table.row_begin, table.row_end
+        # the roads differ in where (ids, rows, n) and the control block come from, and in where the scalars live
+        static = getattr(self.module, "static_grad", None)
+        hyper = self.hyper if self.capturable else None
+        capturing = (hyper is not None or static is not None) and torch.cuda.is_current_stream_capturing()
+        if capturing and hyper is None:
+            # the step-dependent scalars are launch arguments: a replayed graph would repeat them as captured
+            if self.kind == "adam":
+                raise ValueError("FGramOptimizer.step under capture: Adam's bias correction depends on the step count, which a "
+                                 "replayed graph would repeat as captured; use sgd, adagrad or rowwise_adagrad, or step eagerly")
+            if self.rounding == "stochastic":
+                raise ValueError("FGramOptimizer.step under capture: stochastic rounding draws its bits from the step count, which "
+                                 "a replayed graph would repeat as captured; use rounding='nearest', or step eagerly")
+        table = self.module.cache.to_device()
+        if static is not None:                           # the triple of a static backward: the count is on the device
+            ids, rows, n = static
+        else:                                            # the gradient on the module
+            if capturing:
+                raise ValueError("FGramOptimizer.step under capture needs a module built with static_rows= (the default backward "
+                                 "synchronises)")
+            grad = self._current_grad()
+            if grad is None:
+                return 0
+            ids, rows = grad
+            n = None
+            if hyper is not None:                        # the _dh calls read the count from a device word the optimizer keeps
+                ids, rows = ids.contiguous(), rows.contiguous()
+                n = self._n_word.fill_(ids.numel())
+        if capturing:
+            self._need_warm_up(ctl_road)
+        if hyper is not None:
+            if isinstance(grad_scale, torch.Tensor):
+                if grad_scale.dtype != torch.float64 or grad_scale.numel() != 1 or grad_scale.device != table.device:
+                    raise ValueError(f"FGramOptimizer.step: a grad_scale on the device must be one float64 on {table.device}")
+                hyper.grad_scale.copy_(grad_scale.reshape(()))
+            elif grad_scale is not None:
+                hyper.grad_scale.fill_(float(grad_scale))
         ctl = None
         if ctl_road:
-            if extra_sqnorm is None:
-                extra = []
-            elif isinstance(extra_sqnorm, (list, tuple)):
-                extra = list(extra_sqnorm)
+            if static is not None:
+                out, sq, scratch = self._static_control(table, rows.shape[0])
+                sq = table.grad_sqnorm(rows, scratch, n=n, out=sq)[0]
             else:
-                extra = [extra_sqnorm]
-            ctl = table.grad_ctl([table.grad_sqnorm(grad_rows)[0], *extra], grad_scale=grad_scale, max_norm=max_norm,
-                                 skip_nonfinite=skip_nonfinite)
+                out, sq = None, table.grad_sqnorm(rows)[0]
+            scale = dict(grad_scale=grad_scale) if hyper is None else dict(hyper=hyper)
+            ctl = table.grad_ctl([sq, *self._extra_terms(extra_sqnorm)], max_norm=max_norm, skip_nonfinite=skip_nonfinite, out=out,
+                                 **scale)
             self.last_ctl = ctl
-        self.t += 1
-        self._ensure_state()
-
-        def own(x):                                      # the rows this handle owns: a contiguous view
-            return None if x is None else x[lo:hi]
-
-        if self.in_place:
-            table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, row_state=own(self.state2), eps=self.eps,
-                                weight_decay=self.weight_decay, grad_scale=grad_scale, rounding=self.rounding, seed=self.seed,
-                                step=self.t, ctl=ctl)
-            return int(row_ids.numel())
-        weight = module.weight
-        if self.kind == "rowwise_adagrad":
-            table.opt_step_lean(row_ids, grad_rows, kind=self.kind, lr=self.lr, master=own(weight.detach()),
-                                row_state=own(self.state2), eps=self.eps, weight_decay=self.weight_decay, grad_scale=grad_scale,
-                                step=self.t, ctl=ctl)
+        if hyper is not None:
+            table.opt_hyper_advance(hyper, self.kind, ctl)     # the count and the scalars: on the device
         else:
-            table.opt_step(row_ids, grad_rows, own(weight.detach()), kind=self.kind, lr=self.lr, step=self.t, state1=own(self.state1),
-                           state2=own(self.state2), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
-                           grad_scale=grad_scale, ctl=ctl)
-        module._touched = []                             # the served table is current: commit() has nothing to store
-        return int(row_ids.numel())
+            self.t += 1
+        self._ensure_state()
+        self._launch_step(ids, rows, grad_scale=grad_scale, ctl=ctl, n=n, hyper=hyper)
+        if hyper is not None and static is None:
+            stream = torch.cuda.current_stream(table.device)
+            ids.record_stream(stream)                    # they may be temporaries of the caller (the n= calls record nothing)
+            rows.record_stream(stream)
+        return int(ids.numel())
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         if getattr(self.module, "_static", None) is not None:

@@ -2,10 +2,10 @@
 
 Every case calls the C ABI directly and pins the exact return code and the exact `scone_last_error` text of one refusal branch
 of `scone_embed`, `scone_embed_base`, `scone_embed_varlen`, `scone_embed_base_varlen`, `scone_embed_select`,
-`scone_gather_reduce`, `scone_embed_partial`, `scone_finalize`, `scone_embed_prefetch`, `scone_opt_step` and
-`scone_opt_step_lean`; the texts are literals (callers and other tests match on them).  Doubly-wrong calls pin which refusal
-wins, the zero-size calls pin which checks come before the early `SCONE_OK` (they pass null pointers that must not be touched),
-and the shard embeds are covered as far as their "no planned batch" refusal (the rest needs an exchange: test_gpu_multiprocess,
+`scone_gather_reduce`, `scone_embed_partial`, `scone_finalize`, `scone_embed_prefetch`, `scone_opt_step`,
+`scone_opt_step_lean` and the `_ctl`, `_dn` and `_dh` forms of those two; the texts are literals (callers and other tests match
+on them).  Doubly-wrong calls pin which refusal wins, the zero-size calls pin which checks come before the early `SCONE_OK`
+(they pass null pointers that must not be touched), and the shard embeds are covered as far as their "no planned batch" refusal (the rest needs an exchange: test_gpu_multiprocess,
 test_distributed_gloo).
 
 No call here reaches a kernel launch: a refused call returns before one, an early return has nothing to do.  Every non-null
@@ -495,6 +495,130 @@ def test_scone_opt_step_lean(w):
        n=0, master=None)
     w.accepted("scone_opt_step_lean", w.i8, _lean(w, cfg=_lean_cfg(w, **rowwise), n=0, ids=None, grad=None))
     w.accepted("scone_opt_step_lean", w.f20, _lean(w, n=0, ids=None, grad=None, master=None))
+
+
+# ------------------------------------------------------------------ the _ctl, _dn and _dh forms of the two steps
+# `n` is n_cap where the count is on the device; the _dh forms take the kind (and the rounding) where the others take the cfg.
+# `need`: the pointers a form adds that must not be null, in the order they are refused (d_ctl of a _dn / _dh call is optional)
+OPT_FORMS = {
+    "scone_opt_step_ctl": (("cfg", "ids", "grad", "n", "master", "s1", "s2", "ctl", "stream"), ("ctl",)),
+    "scone_opt_step_dn": (("cfg", "ids", "grad", "dn", "n", "master", "s1", "s2", "ctl", "stream"), ("dn",)),
+    "scone_opt_step_dh": (("kind", "ids", "grad", "dn", "n", "master", "s1", "s2", "hyper", "ctl", "stream"), ("dn", "hyper")),
+}
+LEAN_FORMS = {
+    "scone_opt_step_lean_ctl": (("cfg", "ids", "grad", "n", "master", "state", "ctl", "stream"), ("ctl",)),
+    "scone_opt_step_lean_dn": (("cfg", "ids", "grad", "dn", "n", "master", "state", "ctl", "stream"), ("dn",)),
+    "scone_opt_step_lean_dh": (("kind", "rounding", "ids", "grad", "dn", "n", "master", "state", "hyper", "ctl", "stream"),
+                               ("dn", "hyper")),
+}
+NULL_OF = {"ctl": "null d_ctl", "dn": "null d_n", "hyper": "null d_hyper"}
+
+
+def _form(w, order, default_cfg, **kw):
+    a = dict(cfg=default_cfg, kind=0, rounding=0, ids=w.P, grad=w.P, n=4, master=w.P, s1=None, s2=None, state=None, ctl=w.P, dn=w.P,
+             hyper=w.P, stream=None)
+    assert set(kw) <= set(order), set(kw) - set(order)
+    a.update(kw)
+    return tuple(a[k] for k in order)
+
+
+@pytest.mark.parametrize("name", list(OPT_FORMS))
+def test_scone_opt_step_forms(w, name):
+    E = w.L.EINVAL
+    order, need = OPT_FORMS[name]
+    dh = name.endswith("_dh")
+    no = lambda t, text, **kw: w.refused(name, t, _form(w, order, _opt_cfg(w), **kw), E, f"{name}: {text}")  # noqa: E731
+    kind = lambda k: dict(kind=k) if dh else dict(cfg=_opt_cfg(w, kind=k))  # noqa: E731
+    adam, adagrad, bad = kind(w.L.OPT_ADAM), kind(w.L.OPT_ADAGRAD), kind(9)
+    w.null_handle(name, _form(w, order, _opt_cfg(w)))
+    no(w.i8, "bad kind", **bad)
+    no(w.i8, "bad kind", **kind(-1))
+    if not dh:                                                                    # the cfg is scone_opt_step's, checked as there
+        no(w.i8, "null cfg", cfg=None)
+        no(w.i8, "cfg.struct_size does not match this library", cfg=_opt_cfg(w, struct_size=60))
+        no(w.i8, "lr, beta1, beta2, eps, weight_decay and grad_scale must be finite", cfg=_opt_cfg(w, lr=float("nan")))
+        no(w.i8, "Adam needs step >= 1", cfg=_opt_cfg(w, kind=w.L.OPT_ADAM, step=0), s1=w.P, s2=w.P)
+    no(w.index_only, "handle has no table (dim == 0)")
+    for p in need:
+        no(w.i8, NULL_OF[p], **{p: None})
+    for kw in (dict(ids=None), dict(grad=None), dict(master=None)):
+        no(w.i8, "null pointer", **kw)
+    no(w.i8, "Adam needs d_state1 (m)", s2=w.P, **adam)
+    state2 = "Adam / Adagrad need d_state2 (v / the sum of squares)"
+    no(w.i8, state2, s1=w.P, **adam)
+    no(w.i8, state2, **adagrad)
+    # which refusal wins: the cfg (the kind), the table, the form's own pointers in their order, the data pointers, the states
+    no(w.index_only, "bad kind", **bad)
+    no(w.index_only, "handle has no table (dim == 0)", **{need[0]: None})
+    for p in need:
+        no(w.i8, "bad kind", **bad, **{p: None})
+        no(w.i8, NULL_OF[p], n=0, **{p: None})
+        no(w.i8, NULL_OF[p], ids=None, **{p: None})
+    if dh:
+        no(w.i8, "null d_n", dn=None, hyper=None)
+    no(w.i8, "null pointer", ids=None, **adam)
+    no(w.i8, "Adam needs d_state1 (m)", **adam)
+    # n == 0: the cfg, the handle and the form's own pointers are checked first, the data pointers never
+    no(w.i8, "bad kind", n=0, **bad)
+    no(w.index_only, "handle has no table (dim == 0)", n=0)
+    w.accepted(name, w.i8, _form(w, order, _opt_cfg(w), n=0, ids=None, grad=None, master=None, **adam))
+    if "ctl" not in need:                                                         # the block is optional beside a device count
+        w.accepted(name, w.i8, _form(w, order, _opt_cfg(w), n=0, ids=None, grad=None, master=None, ctl=None))
+
+
+@pytest.mark.parametrize("name", list(LEAN_FORMS))
+def test_scone_opt_step_lean_forms(w, name):
+    E = w.L.EINVAL
+    order, need = LEAN_FORMS[name]
+    dh = name.endswith("_dh")
+    no = lambda t, text, **kw: w.refused(name, t, _form(w, order, _lean_cfg(w), **kw), E, f"{name}: {text}")  # noqa: E731
+    cfg = lambda **c: c if dh else dict(cfg=_lean_cfg(w, **c))  # noqa: E731
+    stochastic, rowwise = cfg(rounding=w.L.ROUND_STOCHASTIC), cfg(kind=w.L.LEAN_ROWWISE_ADAGRAD)
+    w.null_handle(name, _form(w, order, _lean_cfg(w)))
+    no(w.i8, "bad kind", **cfg(kind=2))
+    no(w.i8, "bad rounding", **cfg(rounding=2))
+    if not dh:                                                                    # the cfg is scone_opt_step_lean's, checked as there
+        no(w.i8, "null cfg", cfg=None)
+        no(w.i8, "cfg.struct_size does not match this library", cfg=_lean_cfg(w, struct_size=56))
+        no(w.i8, "cfg.reserved must be 0", cfg=_lean_cfg(w, reserved=1))
+        no(w.i8, "lr, eps, weight_decay and grad_scale must be finite", cfg=_lean_cfg(w, eps=float("nan")))
+    no(w.index_only, "handle has no table (dim == 0)")
+    for p in need:
+        no(w.i8, NULL_OF[p], **{p: None})
+    in_place = "in place (d_master == NULL) needs an fp32 or bf16 table, this one is int8"
+    with_master = "stochastic rounding with a master: there is nothing to round"
+    on_fp32 = "stochastic rounding on an fp32 table: there is nothing to round"
+    no(w.i8, in_place, master=None)
+    no(w.i8, with_master, **stochastic)
+    no(w.f20, on_fp32, master=None, **stochastic)
+    no(w.i8, "null pointer", ids=None)
+    no(w.i8, "null pointer", grad=None)
+    state = "row-wise Adagrad needs d_row_state (one fp32 per owned row)"
+    no(w.i8, state, **rowwise)
+    # which refusal wins: the cfg (kind, then rounding), the table, the form's own pointers in their order, the mode, the data
+    # pointers, the state
+    no(w.i8, "bad kind", **cfg(kind=2, rounding=2))
+    no(w.index_only, "bad rounding", **cfg(rounding=2))
+    no(w.index_only, "handle has no table (dim == 0)", master=None, **{need[0]: None})
+    for p in need:
+        no(w.i8, "bad rounding", **cfg(rounding=2), **{p: None})
+        no(w.i8, NULL_OF[p], master=None, **{p: None})                            # before the in-place refusal
+        no(w.i8, NULL_OF[p], **stochastic, **{p: None})
+        no(w.i8, NULL_OF[p], n=0, **{p: None})
+    if dh:
+        no(w.i8, "null d_n", dn=None, hyper=None)
+    no(w.i8, in_place, master=None, **stochastic)
+    no(w.f20, with_master, **stochastic)
+    no(w.i8, in_place, master=None, ids=None)
+    no(w.i8, "null pointer", ids=None, **rowwise)
+    # n == 0: the mode refusals come first, the data pointers never
+    no(w.i8, in_place, n=0, master=None)
+    no(w.f20, on_fp32, n=0, master=None, **stochastic)
+    no(w.i8, "bad kind", n=0, **cfg(kind=2))
+    w.accepted(name, w.i8, _form(w, order, _lean_cfg(w), n=0, ids=None, grad=None, **rowwise))
+    w.accepted(name, w.f20, _form(w, order, _lean_cfg(w), n=0, ids=None, grad=None, master=None))
+    if "ctl" not in need:                                                         # the block is optional beside a device count
+        w.accepted(name, w.f20, _form(w, order, _lean_cfg(w), n=0, ids=None, grad=None, master=None, ctl=None))
 
 
 # ------------------------------------------------------------------ the shard embeds without a planned batch

@@ -69,7 +69,7 @@ build)
   make -C $C -j8 > /dev/null || exit 1
   # in bounds: the same launch with the same arguments; ids and gradient rows are valid whenever it runs (a list that is not
   # ascending or owned would be skipped by the kernel's own id rules anyway)
-  mutate opt_null_stream scone_opt 's|dim3(blocks), dim3(256), 0, s, a.ids, a.grad,|dim3(blocks), dim3(256), 0, nullptr, a.ids, a.grad,|'
+  mutate opt_null_stream scone_opt 's|dim3(blocks), dim3(256), 0, s, a.ids,$|dim3(blocks), dim3(256), 0, nullptr, a.ids,|'
   # in bounds: nothing is launched differently; the host only waits
   mutate rows_hidden_sync scone_backward '/^extern "C" int scone_backward_rows(/,/^}/ s|^  return SCONE_OK;$|  SCONE_HIP(h, hipStreamSynchronize(s)); return SCONE_OK;|'
   # in bounds: the same launch; every src entry is absent or an index inside its list whenever it runs
