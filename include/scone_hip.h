@@ -415,6 +415,53 @@ int scone_embed_base_varlen(scone_handle *h, const int32_t *d_tok, const int32_t
                             int64_t total_tokens, const void *d_base, const void *d_wpe, int64_t n_pos,
                             const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype,
                             scone_stream_t stream);
+
+/* ---- the fused lookup over a batch's LIVE rows (new here: the reference trains its f-gram embeddings with a separate model,
+ * README.md:21-23, and only bakes them into a table for inference).  The forward dual of scone_backward_rows: the same fused
+ * lookup, with the rows taken from the caller's compact array d_rows [n, dim] keyed by d_row_ids [n] -- the ascending distinct
+ * ids scone_backward_row_ids / scone_backward_rows return for the batch -- and NOT from the handle's table, which is never read
+ * (pinned-host and staged handles are accepted like any other).  An f-gram model's outputs for the f-grams a batch matches go
+ * in; scone_backward_rows of the same plan gives the gradient of exactly this array.
+ * Output bits: with every hit of the batch listed, bit for bit what scone_embed (d_wte / vocab), scone_embed_base (d_base) or
+ * their _varlen forms give on a handle with the same index, max_n and lookup_mode whose F32 / F16 / BF16 table (the type
+ * `dtype` names) holds d_rows[u] in row d_row_ids[u]: that entry's arithmetic, in every rule -- exact widening, the sequential
+ * fp32 sum from +0.0f in the reference's list order, the IEEE mean for K >= 2, (base + fg) + wpe, one rounding to out_dtype, the
+ * replaced base row of lookup_mode longest_suffix, "Ids out of range" for token and position ids.
+ * Base rows: at most one of d_wte and d_base (both: SCONE_EINVAL; neither: the term is omitted).  d_base follows
+ * scone_embed_base: [B * T, dim] (packed: [total_tokens, dim]) in out_dtype, d_out == d_base is the defined in-place call, any
+ * other overlap of the two ranges returns SCONE_EINVAL.
+ * An id that is not listed: a hit whose id is not among the live ids contributes a row of +0.0, K stays the full hit count and
+ * SCONE_ST_BAD_ID is raised.  No address outside d_rows[0, n_live) is ever formed, whatever the list holds; a list that is not
+ * ascending is outside the contract (which listed row a hit then reads is unspecified, but the read stays inside the array).
+ * n_live = n, or min(*d_n, n) when d_n is given -- the count on the device (scone_backward_rows_dn's), read on the stream;
+ * with n_live == 0 every hit is unlisted.
+ * Stream contract: ordered on `stream`, no synchronisation; allocates only the stream's match workspace, as scone_embed does
+ * above its one-launch limit; two launches at every batch size (the match, then the gather over the live rows: a wave
+ * resolves the ids of a group of 8 or 4 consecutive tokens to slots with a lane-parallel lower-bound search, then walks the
+ * group as the unit-walking lookup kernel does); there is no one-launch form.  The packed form adds a launch for the
+ * remainder where scone_embed_varlen does.
+ * B * T == 0 (packed: total_tokens == 0 or n_seqs == 0) returns SCONE_OK before `live` and the pointers are looked at.
+ * SCONE_EINVAL (scone_last_error names the reason): a null live, d_tok or d_out, a null d_row_ids or d_rows with n > 0, a
+ * d_rows that is not 16-byte aligned, a bad struct_size / dtype / out_dtype / reduce, n > 2^31 - 1, dim == 0 or dim % 8 != 0,
+ * a handle that owns only part of the rows (row_begin != 0 or row_end != n_rows: the match records of a shard leave out the
+ * other shards' hits), and the shape, wte / wpe and packed-batch refusals of scone_embed / scone_embed_varlen (negative sizes,
+ * total_tokens > 2^31 - 1, a null d_cu_seqlens, d_wte with vocab <= 0, d_wpe with n_pos <= 0). */
+typedef struct scone_live_rows {
+  uint32_t struct_size;      /* sizeof(scone_live_rows) */
+  int32_t dtype;             /* SCONE_DT_F32 / F16 / BF16: element type of d_rows */
+  const int64_t *d_row_ids;  /* [n] ascending, distinct: what scone_backward_row_ids / scone_backward_rows return */
+  const void *d_rows;        /* [n, dim] contiguous, 16-byte aligned; dim = the handle's */
+  uint64_t n;                /* rows (capacity when d_n is given), <= 2^31 - 1 */
+  const uint64_t *d_n;       /* NULL, or the count on the device: min(*d_n, n) rows are live, read on the stream */
+} scone_live_rows;
+int scone_embed_rows(scone_handle *h, const scone_live_rows *live, const int32_t *d_tok, int32_t B, int32_t T,
+                     const void *d_wte, int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos,
+                     const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, void *stream);
+int scone_embed_rows_varlen(scone_handle *h, const scone_live_rows *live, const int32_t *d_tok, const int32_t *d_cu_seqlens,
+                            int32_t n_seqs, int64_t total_tokens, const void *d_wte, int64_t vocab, const void *d_base,
+                            const void *d_wpe, int64_t n_pos, const int32_t *d_pos, int32_t reduce, void *d_out,
+                            int32_t out_dtype, void *stream);
+
 /* Pinned-host tables with a prefetch pipeline (cfg.stage_tokens > 0): start fetching for the NEXT batch now.  The first chunks
  * of (d_tok, B, T) are matched, their missing cold rows placed in the HBM cache and copied host -> HBM on the handle's side
  * streams, ordered behind `stream` (the stream on which the tokens are produced) -- or, tokens_ready != 0, behind nothing: the

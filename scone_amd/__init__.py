@@ -10,8 +10,8 @@ from scone_amd.tokenization.n_gram_extractor import NGramExtractor
 from scone_amd.tokenization.f_gram_tokenizer import FGramTokenizer
 from scone_amd.inference.embedding_cache import EmbeddingCache
 from scone_amd.models.language_model import SconeEmbedding, SconeLanguageModel
-from scone_amd.training import FGramOptimizer, InPlaceFGramTable, TrainableFGramTable
+from scone_amd.training import FGramOptimizer, InPlaceFGramTable, LiveFGramBatch, TrainableFGramTable
 
 __all__ = ["NGramExtractor", "FGramTokenizer", "EmbeddingCache", "SconeEmbedding", "SconeLanguageModel", "TrainableFGramTable",
-           "InPlaceFGramTable", "FGramOptimizer"]
+           "InPlaceFGramTable", "FGramOptimizer", "LiveFGramBatch"]
 __version__ = "0.1.0"

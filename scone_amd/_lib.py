@@ -118,6 +118,21 @@ class SconeOptHyper(C.Structure):
     ]
 
 
+class SconeLiveRows(C.Structure):
+    """``scone_live_rows``: a batch's live f-gram rows as ``scone_embed_rows`` takes them (include/scone_hip.h, "the fused
+    lookup over a batch's LIVE rows")."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32),
+        ("d_row_ids", C.c_void_p),
+        ("d_rows", C.c_void_p),
+        ("n", C.c_uint64),
+        ("d_n", C.c_void_p),
+    ]
+
+
+LIVE_ROWS_MAX = 2**31 - 1   # the most rows a scone_live_rows may list
+
 _P = C.c_void_p
 _I32, _I64, _U32, _U64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 
@@ -188,6 +203,9 @@ SIGNATURES = {
     "scone_embed_base": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
     "scone_embed_base_varlen": (C.c_int, [_P, _P, _P, _I32, _I64, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
     "scone_embed_select": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
+    "scone_embed_rows": (C.c_int, [_P, C.POINTER(SconeLiveRows), _P, _I32, _I32, _P, _I64, _P, _P, _I64, _P, _I32, _P, _I32, _P]),
+    "scone_embed_rows_varlen": (C.c_int, [_P, C.POINTER(SconeLiveRows), _P, _P, _I32, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _P,
+                                          _I32, _P]),
     "scone_embed_prefetch": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "scone_reserve": (C.c_int, [_P, _I64]),
     "scone_set_cu_reserve": (C.c_int, [_P, _I32]),

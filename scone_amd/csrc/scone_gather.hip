@@ -18,6 +18,7 @@
 // workspace its records, profiled brackets the launch, launch_fmt / launch_select pick the table format's translation unit.
 #include "scone_gather_impl.h"
 #include "scone_embed_select.h"
+#include "scone_embed_rows.h"
 #ifdef SCONE_PROBE_PERM
 #include <cstdlib>
 #endif
@@ -474,6 +475,128 @@ extern "C" int scone_embed_varlen(scone_handle *h, const int32_t *d_tok, const i
   embed_args a = lookup_args(h, total_tokens, (int)total_tokens);
   combine(a, d_tok, d_pos, d_wte, vocab, nullptr, d_wpe, n_pos, reduce, d_out);
   return embed_packed(h, a, d_cu_seqlens, n_seqs, out_dtype, (hipStream_t)stream);
+}
+
+// ---- the fused lookup over a batch's live rows (scone_embed_rows.h): the existing match, then k_embed_rows in the place of
+// the table's gather kernel.  The handle's table is never read, so pinned-host and staged handles take this road as any other.
+namespace {
+int launch_rows(scone_handle *h, const live_rows_view &live, int dtype, const embed_args &a, int out_dtype, hipStream_t s) {
+  switch (dtype) {
+    case SCONE_DT_F32: return launch_rows_f32(h, live, a, out_dtype, s);
+    case SCONE_DT_F16: return launch_rows_f16(h, live, a, out_dtype, s);
+    default: return launch_rows_bf16(h, live, a, out_dtype, s);  // (check_live_ptrs admits three types)
+  }
+}
+// what both live-row entry points check before an empty batch returns: the handle and the scalars
+int check_live_handle(scone_handle *h, const char *who, int32_t reduce, int32_t out_dtype) {
+  if (!h) return SCONE_EINVAL;
+  if (h->cfg.dim <= 0 || h->cfg.dim % 8 != 0) return scone_refuse(h, SCONE_EINVAL, who, "needs a handle with dim > 0 and dim % 8 == 0");
+  if (h->cfg.row_begin != 0 || h->cfg.row_end != h->cfg.n_rows)
+    return scone_refuse(h, SCONE_EINVAL, who, "not for a row-sharded handle (its match records leave out the other shards' hits)");
+  SCONE_TRY(check_reduce(h, who, reduce));
+  return check_out_dtype(h, who, out_dtype);
+}
+// ... and with work to do
+int check_live_ptrs(scone_handle *h, const char *who, const scone_live_rows *live, const void *d_tok, const void *d_out,
+                    const void *d_wte, int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos, long long ntok,
+                    int32_t out_dtype) {
+  if (!live) return scone_refuse(h, SCONE_EINVAL, who, "null live");
+  if (live->struct_size != sizeof(scone_live_rows)) return scone_refuse(h, SCONE_EINVAL, who, "bad struct_size");
+  if (live->dtype != SCONE_DT_F32 && live->dtype != SCONE_DT_F16 && live->dtype != SCONE_DT_BF16)
+    return scone_refuse(h, SCONE_EINVAL, who, "bad dtype (live rows are fp32, fp16 or bf16)");
+  if (live->n > 0x7FFFFFFFull) return scone_refuse(h, SCONE_EINVAL, who, "n above 2^31 - 1");
+  if (!d_tok || !d_out) return scone_refuse(h, SCONE_EINVAL, who, "null pointer (d_tok and d_out are required)");
+  if (live->n && (!live->d_row_ids || !live->d_rows))
+    return scone_refuse(h, SCONE_EINVAL, who, "null pointer (d_row_ids and d_rows are required with n > 0)");
+  if (reinterpret_cast<uintptr_t>(live->d_rows) % 16 != 0) return scone_refuse(h, SCONE_EINVAL, who, "d_rows is not 16-byte aligned");
+  if (d_wte && d_base) return scone_refuse(h, SCONE_EINVAL, who, "d_wte and d_base are exclusive");
+  SCONE_TRY(check_wte_wpe(h, who, d_wte, vocab, d_wpe, n_pos));
+  if (d_base) SCONE_TRY(check_base(h, who, d_base, d_out, ntok, out_dtype));
+  return SCONE_OK;
+}
+live_rows_view live_view(const scone_live_rows *live) {
+  live_rows_view v;
+  v.rows = reinterpret_cast<const uint8_t *>(live->d_rows), v.ids = live->d_row_ids;
+  v.n = live->n, v.d_n = reinterpret_cast<const unsigned long long *>(live->d_n);
+  return v;
+}
+// the handle's part of the lookup without its table: the records, the zero row, the lookup mode, the status word
+embed_args rows_args(const scone_handle *h, long long ntok, int T) {
+  embed_args a = {};
+  a.tv.d = h->cfg.dim;
+  a.BT = ntok, a.ntok = ntok, a.T = T, a.max_n = h->cfg.max_n;
+  a.zero_row = h->d_zero_row, a.mode = (int)h->cfg.lookup_mode, a.status = h->d_status;
+  return a;
+}
+}  // namespace
+
+extern "C" int scone_embed_rows(scone_handle *h, const scone_live_rows *live, const int32_t *d_tok, int32_t B, int32_t T,
+                                const void *d_wte, int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos,
+                                const int32_t *d_pos, int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream) {
+  const char *who = "scone_embed_rows";
+  SCONE_TRY(check_live_handle(h, who, reduce, out_dtype));
+  SCONE_TRY(check_shape(h, who, B, T));
+  const long long BT = (long long)B * T;
+  if (BT == 0) return SCONE_OK;
+  SCONE_TRY(check_live_ptrs(h, who, live, d_tok, d_out, d_wte, vocab, d_base, d_wpe, n_pos, BT, out_dtype));
+  SCONE_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  embed_args a = rows_args(h, BT, T);
+  combine(a, d_tok, d_pos, d_wte, vocab, d_base, d_wpe, n_pos, reduce, d_out);
+  // the workspace of THIS stream, held while the match that writes it and the lookup that reads it are enqueued
+  scone_ws_lock ws(scone_ws_acquire(h, s));
+  if (!ws.w) return scone_refuse(h, SCONE_ENOMEM, who, "out of memory");
+  SCONE_TRY(scone_ensure_ell(h, ws.w, BT));
+  SCONE_TRY(scone_launch_match_ell(h, d_tok, B, T, ws.w->d_ell, s));
+  a.ell = ws.w->d_ell;
+  const live_rows_view lv = live_view(live);
+  return profiled(h, s, [&] { return launch_rows(h, lv, live->dtype, a, out_dtype, s); });
+}
+
+// Packed batch: k_match_ell_varlen leaves one record and one position per token, as in embed_packed, and the same traversal
+// follows ([total / T', T'] plus the remainder when SCONE_VARLEN_T or a stream above 2^25 tokens asks for rows).
+extern "C" int scone_embed_rows_varlen(scone_handle *h, const scone_live_rows *live, const int32_t *d_tok,
+                                       const int32_t *d_cu_seqlens, int32_t n_seqs, int64_t total_tokens, const void *d_wte,
+                                       int64_t vocab, const void *d_base, const void *d_wpe, int64_t n_pos, const int32_t *d_pos,
+                                       int32_t reduce, void *d_out, int32_t out_dtype, scone_stream_t stream) {
+  const char *who = "scone_embed_rows_varlen";
+  SCONE_TRY(check_live_handle(h, who, reduce, out_dtype));
+  if (n_seqs < 0 || total_tokens < 0) return scone_refuse(h, SCONE_EINVAL, who, "negative n_seqs or total_tokens");
+  SCONE_TRY(check_total(h, who, total_tokens));
+  if (total_tokens == 0 || n_seqs == 0) return SCONE_OK;
+  if (!d_cu_seqlens) return scone_refuse(h, SCONE_EINVAL, who, "null pointer (d_cu_seqlens is required)");
+  SCONE_TRY(check_live_ptrs(h, who, live, d_tok, d_out, d_wte, vocab, d_base, d_wpe, n_pos, total_tokens, out_dtype));
+  SCONE_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  const long long total = total_tokens;
+  embed_args a = rows_args(h, total, (int)total);
+  combine(a, d_tok, d_pos, d_wte, vocab, d_base, d_wpe, n_pos, reduce, d_out);
+  scone_ws_lock ws(scone_ws_acquire(h, s));
+  if (!ws.w) return scone_refuse(h, SCONE_ENOMEM, who, "out of memory");
+  SCONE_TRY(scone_ensure_ell(h, ws.w, total));
+  int32_t *vpos = nullptr;
+  if (a.wpe && !a.pos) {  // default positions p - cu[s]: written by the match
+    SCONE_TRY(scone_ensure_vpos(h, ws.w, total));
+    vpos = ws.w->d_vpos;
+    a.pos = vpos;
+  }
+  SCONE_TRY(scone_launch_match_ell_varlen(h, d_tok, d_cu_seqlens, n_seqs, total, ws.w->d_ell, vpos, s));
+  a.ell = ws.w->d_ell;
+  const long long row = h->varlen_t > 0 ? h->varlen_t : (total <= (1ll << 25) ? total : 512);
+  const long long Tp = total < row ? total : row;
+  const long long main_tok = total / Tp * Tp;
+  const live_rows_view lv = live_view(live);
+  return profiled(h, s, [&] {
+    embed_args m = slice(a, 0, main_tok, out_dtype);
+    m.T = (int)Tp;
+    int rc = launch_rows(h, lv, live->dtype, m, out_dtype, s);
+    if (!rc && main_tok < total) {
+      embed_args r = slice(a, main_tok, total - main_tok, out_dtype);
+      r.T = (int)r.BT;
+      rc = launch_rows(h, lv, live->dtype, r, out_dtype, s);
+    }
+    return rc;
+  });
 }
 
 // The fused lookup at chosen positions only (scone_embed_select.h): one launch of ceil(n_sel / 4) workgroups, no workspace, no

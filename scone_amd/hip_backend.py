@@ -1229,6 +1229,113 @@ class SconeTable:
             self._check(rc, "scone_embed_base_varlen")
         return out
 
+    def embed_rows(self, tok: torch.Tensor, row_ids: torch.Tensor, rows: torch.Tensor, *, n: Optional[torch.Tensor] = None,
+                   cu_seqlens=None, wte: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
+                   base: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None, reduce: str = "mean",
+                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_embed_rows`` / ``scone_embed_rows_varlen``: the fused lookup over a batch's LIVE rows -> ``[B, T, d]``
+        (``tok [B, T]``) or ``[total, d]`` (``tok [total]`` with ``cu_seqlens=``).  The rows come from ``rows [U, d]`` (fp32 /
+        fp16 / bf16, on the device) keyed by ``row_ids [U]`` (int64, ascending and distinct: :meth:`BackwardPlan.row_ids`), not
+        from the table, which is never read; the output has the bits :meth:`embed` / :meth:`embed_base` / the packed forms
+        give on a table of ``rows.dtype`` that holds ``rows[u]`` in row ``row_ids[u]``.  A hit whose id is not listed adds a
+        row of zeros (the divisor stays the full hit count) and raises bit 1 of :meth:`status`.  ``n``: an int64 device scalar,
+        ``min(n, U)`` rows are live (read on the stream).  ``wte`` and ``base`` are exclusive; ``out=base`` is the in-place
+        call; ``pos`` are explicit position ids.  Every argument check raises :class:`SconeInvalidArgument` before any device
+        work; a ``rows`` that is not contiguous or not 16-byte aligned is copied.  Stream-ordered, two launches."""
+        who = "embed_rows"
+        if not isinstance(tok, torch.Tensor) or not isinstance(row_ids, torch.Tensor) or not isinstance(rows, torch.Tensor):
+            raise SconeInvalidArgument(f"{who}: tok, row_ids and rows must be tensors")
+        packed = cu_seqlens is not None
+        if packed:
+            if tok.dim() != 1:
+                raise SconeInvalidArgument(f"{who}: with cu_seqlens= the packed token ids are a 1-D tensor [total]")
+            ntok, shape = tok.shape[0], (tok.shape[0], self.dim)
+            if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda):
+                try:
+                    cu_seqlens = check_cu_seqlens(cu_seqlens, ntok)
+                except ValueError as e:
+                    raise SconeInvalidArgument(f"{who}: {e}") from None
+            elif not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                      and cu_seqlens.numel() >= 1):
+                raise SconeInvalidArgument(f"{who}: a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+        else:
+            if tok.dim() == 1:
+                tok = tok.unsqueeze(0)
+            if tok.dim() != 2:
+                raise SconeInvalidArgument(f"{who}: token ids must be [T] or [B, T]")
+            ntok, shape = tok.numel(), (tok.shape[0], tok.shape[1], self.dim)
+        if row_ids.dtype != torch.int64 or row_ids.dim() != 1:
+            raise SconeInvalidArgument(f"{who}: row_ids must be a 1-D int64 tensor, got {row_ids.dtype} {tuple(row_ids.shape)}")
+        if rows.dtype not in _DT:
+            raise SconeInvalidArgument(f"{who}: rows must be float32, float16 or bfloat16, not {rows.dtype}")
+        if rows.dim() != 2 or rows.shape[1] != self.dim or rows.shape[0] != row_ids.shape[0]:
+            raise SconeInvalidArgument(f"{who}: rows must be [{row_ids.shape[0]}, {self.dim}] (one row per row id), "
+                                       f"got {tuple(rows.shape)}")
+        if rows.shape[0] > L.LIVE_ROWS_MAX:
+            raise SconeInvalidArgument(f"{who}: at most 2^31 - 1 live rows")
+        if self.dim % 8 != 0:
+            raise SconeInvalidArgument(f"{who}: needs d % 8 == 0")
+        if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int64 and n.numel() == 1):
+            raise SconeInvalidArgument(f"{who}: n must be an int64 tensor of one element (the live count on the device)")
+        if reduce not in _REDUCE:
+            raise SconeInvalidArgument(f"{who}: unknown reduce {reduce!r}")
+        if wte is not None and base is not None:
+            raise SconeInvalidArgument(f"{who}: wte and base are exclusive")
+        if out_dtype is None:
+            out_dtype = next((t.dtype for t in (base, wte, wpe, out) if t is not None), torch.float32)
+        if out_dtype not in _DT:
+            raise SconeInvalidArgument(f"{who}: out_dtype must be float32, float16 or bfloat16")
+        if base is not None and not (isinstance(base, torch.Tensor) and base.dim() >= 2 and base.shape[-1] == self.dim
+                                     and base.numel() == ntok * self.dim and (not packed or base.dim() == 2)):
+            raise SconeInvalidArgument(f"{who}: base must hold {ntok} rows of {self.dim}" + (f": [{ntok}, {self.dim}]" if packed else "")
+                                       + f", got {tuple(base.shape) if isinstance(base, torch.Tensor) else type(base).__name__}")
+        for name, w in (("base", base), ("wte", wte), ("wpe", wpe)):
+            if w is not None and not (w.is_cuda and w.is_contiguous() and w.dtype == out_dtype and w.dim() >= 2
+                                      and w.shape[-1] == self.dim):
+                raise SconeInvalidArgument(f"{who}: {name} must be a contiguous [*, {self.dim}] {out_dtype} tensor on the device")
+        if pos is not None and not (isinstance(pos, torch.Tensor) and not pos.dtype.is_floating_point):
+            raise SconeInvalidArgument(f"{who}: pos must be an integer tensor")
+        if pos is not None and packed and pos.numel() != ntok:
+            raise SconeInvalidArgument(f"{who}: pos must hold one position per packed token ({ntok})")
+        if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype == out_dtype and out.numel() == ntok * self.dim):
+            raise SconeInvalidArgument(f"{who}: out must be a contiguous {out_dtype} tensor of {ntok} rows of {self.dim} on the device")
+        # ---- device work from here
+        if not (tok.dtype == torch.int32 and tok.is_cuda and tok.is_contiguous()):
+            tok = tok.to(device=self.device, dtype=torch.int32).contiguous()
+        row_ids = row_ids.to(device=self.device).contiguous()
+        rows = rows.to(device=self.device)
+        if not rows.is_contiguous() or rows.data_ptr() % 16 != 0:
+            rows = rows.contiguous() if not rows.is_contiguous() else rows.clone()
+        if n is not None:
+            n = n.to(device=self.device).reshape(1)
+        if pos is not None:
+            pos = pos.to(device=self.device, dtype=torch.int32)
+            pos = (pos.reshape(-1) if packed else pos.expand(tok.shape)).contiguous()
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=self.device)
+        live = L.SconeLiveRows(C.sizeof(L.SconeLiveRows), _DT[rows.dtype], row_ids.data_ptr() or None, rows.data_ptr() or None,
+                               rows.shape[0], None if n is None else n.data_ptr())
+        tail = (None if wte is None else wte.data_ptr(), 0 if wte is None else wte.shape[0],
+                None if base is None else base.data_ptr(), None if wpe is None else wpe.data_ptr(),
+                0 if wpe is None else wpe.shape[0], None if pos is None else pos.data_ptr(), _REDUCE[reduce], out.data_ptr(),
+                _DT[out_dtype], torch.cuda.current_stream(self.device).cuda_stream)
+        if packed:
+            cu = cu_seqlens if isinstance(cu_seqlens, torch.Tensor) else torch.from_numpy(cu_seqlens).to(self.device)
+            name = "scone_embed_rows_varlen"
+            rc = L.lib().scone_embed_rows_varlen(self._h, C.byref(live), tok.data_ptr(), cu.data_ptr(), cu.numel() - 1, ntok, *tail)
+        else:
+            name = "scone_embed_rows"
+            rc = L.lib().scone_embed_rows(self._h, C.byref(live), tok.data_ptr(), tok.shape[0], tok.shape[1], *tail)
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"{name}: {L.lib().scone_last_error(self._h).decode()} [{L.lib().scone_strerror(rc).decode()}]")
+        if rc != L.OK:
+            self._check(rc, name)
+        stream = torch.cuda.current_stream(self.device)
+        for x in (rows, row_ids, tok, n, pos):            # they may be temporaries made here
+            if x is not None and x.numel():
+                x.record_stream(stream)
+        return out
+
     def embed_select(self, tok: torch.Tensor, sel, *, cu_seqlens=None, wte: Optional[torch.Tensor] = None,
                      base: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
                      position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",

@@ -355,6 +355,70 @@ class EmbeddingCache:
         with table.backward_plan(torch.as_tensor(input_ids), cu_seqlens) as plan:
             return plan.rows(grad_out, reduce)
 
+    # ------------------------------------------------------------------ training an f-gram model through the lookup
+    def f_gram_keys(self, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(tokens [N, max_n] int64, lens [N] int64)`` on the device: the token ids of every f-gram, row == id, ``tokens`` 0
+        beyond ``lens`` -- an f-gram model's input.  Built once from ``NGramExtractor.key_arrays()``; later calls return the
+        same tensors."""
+        if device is None:
+            device = self.to_device().device
+        device = torch.device(device)
+        cached = getattr(self, "_f_gram_keys", None)
+        if cached is None or cached[0].device != device:
+            keys, lens = self.n_gram_extractor.key_arrays()
+            lens64 = np.asarray(lens).astype(np.int64)
+            tokens = np.asarray(keys).astype(np.int64) * (np.arange(keys.shape[1])[None, :] < lens64[:, None])
+            cached = (torch.from_numpy(np.ascontiguousarray(tokens)).to(device), torch.from_numpy(lens64).to(device))
+            self._f_gram_keys = cached
+        return cached
+
+    def live_rows(self, input_ids: torch.Tensor, cu_seqlens=None):
+        """The :class:`~scone_amd.LiveFGramBatch` of a batch (``input_ids [B, T]``, or ``[total]`` with ``cu_seqlens=``): the
+        distinct f-grams it matches (``row_ids``, ``tokens``, ``lens``) and ``embed(rows)``, the fused lookup over rows computed
+        for exactly those f-grams, differentiable in them -- the training loop of an f-gram model::
+
+            with cache.live_rows(ids) as lb:
+                y = lb.embed(proj(model(lb.tokens, lb.lens)), base=wte(ids), wpe=...)
+
+        Builds one backward plan (one synchronise, which reads the number of distinct rows)."""
+        tok = torch.as_tensor(input_ids)
+        if tok.dtype.is_floating_point or tok.dtype == torch.bool:
+            raise ValueError("live_rows: input_ids must hold integers")
+        if cu_seqlens is not None:
+            if tok.dim() != 1:
+                raise ValueError("live_rows: with cu_seqlens=, input_ids must be the 1-D packed token ids [total]")
+            if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda):
+                from scone_amd.hip_backend import check_cu_seqlens
+                cu_seqlens = check_cu_seqlens(cu_seqlens, tok.shape[0])      # before any device work
+        elif tok.dim() not in (1, 2):
+            raise ValueError("live_rows: input_ids must be [T] or [B, T] (or [total] with cu_seqlens=)")
+        if self.embedding_dim % 8 != 0:
+            raise ValueError("live_rows: the lookup over live rows needs embedding_dim % 8 == 0")
+        from scone_amd.training import LiveFGramBatch
+        return LiveFGramBatch(self, tok, cu_seqlens)
+
+    def bake(self, fn, chunk_rows: int = 65536) -> None:
+        """Turn a trained f-gram model into the served table: for id ranges of ``chunk_rows``, ``fn(tokens [n, max_n], lens [n])
+        -> [n, d]`` (the slices of :meth:`f_gram_keys`) is stored with ``store_f32(..., row0=)`` -- quantised on the device
+        into the table's format, without ever holding ``[N, d]`` in fp32."""
+        if not callable(fn):
+            raise ValueError("bake: fn must be callable: fn(tokens [n, max_n], lens [n]) -> [n, d]")
+        if isinstance(chunk_rows, bool) or not isinstance(chunk_rows, (int, np.integer)) or int(chunk_rows) < 1:
+            raise ValueError("bake: chunk_rows must be a positive integer")
+        chunk_rows = int(chunk_rows)
+        table = self.to_device()
+        tokens, lens = self.f_gram_keys(table.device)
+        n_rows = min(int(tokens.shape[0]), table.n_rows)
+        with torch.no_grad():
+            for r0 in range(0, n_rows, chunk_rows):
+                r1 = min(r0 + chunk_rows, n_rows)
+                rows = fn(tokens[r0:r1], lens[r0:r1])
+                if not (isinstance(rows, torch.Tensor) and tuple(rows.shape) == (r1 - r0, self.embedding_dim)):
+                    raise ValueError(f"bake: fn must return a [{r1 - r0}, {self.embedding_dim}] tensor for rows [{r0}, {r1})")
+                table.store_f32(rows.float(), row0=r0)
+        if self._present is not None:
+            self._present[:n_rows] = True
+
     def _embed_tokens_base(self, input_ids, base, reduce, wte, wpe, position_ids, out_dtype, out, check, cu_seqlens):
         """``embed_tokens(base=...)``; every ``ValueError`` here is raised before any device work."""
         d = self.embedding_dim

@@ -154,6 +154,96 @@ class _Lookup(torch.autograd.Function):
         return grad_weight, grad_base, None, None, None, None, None
 
 
+class _LiveLookup(torch.autograd.Function):
+    """:meth:`LiveFGramBatch.embed` on the tape: the forward is ``scone_embed_rows`` on the batch's live rows, the backward
+    the plan's deterministic row gradient -- ``[U, d]``, row ``u`` belonging to ``row_ids[u]``: the gradient of ``rows``."""
+
+    @staticmethod
+    def forward(ctx, rows, base, batch, wte, wpe, position_ids, reduce, out_dtype, out):
+        y = batch.table.embed_rows(batch.input_ids, batch.plan.row_ids(), rows.detach(), cu_seqlens=batch.cu_seqlens, wte=wte, wpe=wpe,
+                                   base=None if base is None else base.detach(), pos=position_ids, reduce=reduce,
+                                   out_dtype=out_dtype, out=out)
+        if out is not None:
+            ctx.mark_dirty(out)
+        ctx.batch, ctx.reduce, ctx.rows_dtype = batch, reduce, rows.dtype
+        ctx.base_dtype = None if base is None else base.dtype
+        ctx.base_shape = None if base is None else base.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch = ctx.batch
+        grad_rows = grad_base = None
+        grad_out = grad_out.contiguous()
+        if ctx.needs_input_grad[0]:
+            grad_rows = batch.plan.rows(grad_out, ctx.reduce)[1].to(ctx.rows_dtype)
+        if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
+            grad_base = grad_out                                     # as _Lookup returns it
+            if batch.cache.lookup_mode == "longest_suffix":          # a matched f-gram replaced the base row
+                grad_base = grad_out * (batch.plan.counts() == 0).reshape(*grad_out.shape[:-1], 1)
+            grad_base = grad_base.to(ctx.base_dtype).reshape(ctx.base_shape)
+        return grad_rows, grad_base, None, None, None, None, None, None, None
+
+
+class LiveFGramBatch:
+    """The f-grams one batch matches, and the fused lookup over rows computed for them: what connects an f-gram MODEL to the
+    lookup during training (the reference trains its f-gram embeddings with a separate model and only bakes them into a table
+    for inference, README.md:21-23).  Made by :meth:`EmbeddingCache.live_rows`; a context manager, ``close()`` frees the plan.
+
+    ``row_ids [U]`` (int64, ascending) are the distinct f-gram ids the batch hits, ``tokens [U, max_n]`` / ``lens [U]`` their
+    token ids (0 beyond ``lens``) -- the f-gram model's input.  :meth:`embed` looks the batch up in ``rows [U, d]``, the model's
+    output for exactly those f-grams, and is differentiable in ``rows`` and ``base``; :meth:`store` writes rows into the served
+    table."""
+
+    def __init__(self, cache: EmbeddingCache, input_ids: torch.Tensor, cu_seqlens=None) -> None:
+        self.cache = cache
+        self.table = table = cache.to_device()
+        tok = torch.as_tensor(input_ids)
+        if cu_seqlens is None and tok.dim() == 1:
+            tok = tok.unsqueeze(0)
+        self.input_ids = tok.to(device=table.device, dtype=torch.int32).contiguous()
+        self.cu_seqlens = cu_seqlens
+        if cu_seqlens is not None and not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda):
+            from scone_amd.hip_backend import check_cu_seqlens
+            self.cu_seqlens = torch.from_numpy(check_cu_seqlens(cu_seqlens, self.input_ids.shape[0])).to(table.device)
+        self.plan = table.backward_plan(self.input_ids, self.cu_seqlens)      # the one synchronise: it reads U
+        self.row_ids = self.plan.row_ids()
+        keys, lens = cache.f_gram_keys(table.device)
+        self.tokens = keys.index_select(0, self.row_ids)
+        self.lens = lens.index_select(0, self.row_ids)
+
+    def close(self) -> None:
+        self.plan.close()
+
+    def __enter__(self) -> "LiveFGramBatch":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __len__(self) -> int:
+        return int(self.row_ids.shape[0])
+
+    def embed(self, rows: torch.Tensor, *, wte: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
+              base: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",
+              out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``out = (base | wte[input_ids]) + reduce_k rows[slot of f_gram_k] + wpe[position_ids]`` -- :meth:`EmbeddingCache.embed_tokens`
+        with the f-gram rows taken from ``rows [U, d]`` (fp32 / fp16 / bf16; row ``u`` is the row of ``row_ids[u]``), bit
+        for bit what a table of that type holding them would give.  The gradient of ``rows`` is the library's deterministic
+        sparse row gradient (``[U, d]``, cast to ``rows.dtype``); the gradient of ``base`` is ``grad_out`` (``lookup_mode="cover"``)
+        or ``grad_out * (K == 0)`` (``"longest_suffix"``: a matched f-gram replaced the base row).  ``wte`` / ``wpe`` get NO
+        gradient: when they train, pass ``base=wte(input_ids)`` and add the position embeddings outside.  May be called more
+        than once per batch."""
+        return _LiveLookup.apply(rows, base, self, wte, wpe, position_ids, reduce, out_dtype, out)
+
+    def store(self, rows: torch.Tensor) -> None:
+        """Write the batch's rows into the served table at ``row_ids``, whatever its format (``store_f32``)."""
+        if rows.dim() != 2 or tuple(rows.shape) != (len(self), self.table.dim):
+            raise ValueError(f"rows must be [{len(self)}, {self.table.dim}], got {tuple(rows.shape)}")
+        if len(self):
+            self.table.store_f32(rows.detach().float(), ids=self.row_ids)
+
+
 class TrainableFGramTable(nn.Module):
     """The f-gram table of ``cache`` as a trainable module.
 
