@@ -1034,6 +1034,69 @@ int scone_backward_rows_acc(scone_handle *h, scone_bwd_plan *plan, const void *d
                             const uint32_t *d_src_old, const uint32_t *d_src_new, const uint32_t *d_pos_new, uint64_t n_out,
                             const float *d_rows_old, float *d_rows_out, scone_stream_t stream);
 
+/* ---- backward of the dense side: deterministic gradients of wte and wpe (new here; the reference leaves them to autograd,
+ * language_model.py:239-254, whose embedding backward scatters with float atomics).  New entry points only: SCONE_ABI_VERSION is
+ * unchanged, and every other entry point keeps its bits, its refusals and its stream contract.  The section stands here, behind
+ * "gradient accumulation", whose scone_backward_row_ids / scone_backward_rows_acc it uses: the header ends with
+ * scone_embed_select, and the prototypes of the sections in between are counted.  The prototypes spell their stream
+ * `void *stream` (the same type as scone_stream_t), as the section "backward and optimizer step without a host synchronisation".
+ * What it is for: out = (wte[tok] + reduce_k row_k) + wpe[pos].  The sections above give the gradient of the middle term; the
+ * gradient of row i of wte (of wpe) is the sum of grad_out[p, :] over the positions p whose token (position id) is i -- the
+ * table's backward in a second id space, with lists of one element.
+ * Definition.  An INDEX PLAN over d_idx [ntok] int32 and an id space of n_ids ids is the backward plan ("backward", above) of
+ * a batch whose position p has the list [d_idx[p]].  A position has NO reference if d_idx[p] is outside [0, n_ids), or if
+ * d_skip != NULL and d_skip[p] != 0.  K_p is the list length (0 or 1) and the weight is 1.0f.  Everything else is the
+ * contract of "backward", word for word: the references of an id are taken in ascending p and cut into chunks of
+ * C = scone_backward_chunk() consecutive references; a chunk's partial is a = +0.0; a = a + c over its references in order;
+ * an id with one chunk gets that partial, an id with several gets acc = +0.0; acc = acc + partial_j in chunk order; multiply
+ * and add are separate roundings; no atomics on floating-point data anywhere.  The weight being 1.0f, either `reduce` gives
+ * the sum's bits.  Ids out of range are skipped silently: the forward already raises SCONE_ST_BAD_TOKEN for them, and this
+ * backward raises no status bit, as scone_backward_plan raises none.
+ *   scone_backward_plan_index        builds that plan: the (id, p) pairs, sorted stably by id, cut into chunks -- the passes of
+ *                                    scone_backward_plan without its match and without a workspace.  n_ids is INDEPENDENT of the
+ *                                    handle's table (a 50,257-row wte on a table of 40 rows): the plan carries its own id-space
+ *                                    size.  Synchronises the stream ONCE, to return U (the distinct ids with a reference) in
+ *                                    *h_n_rows and the reference count in *h_n_refs (either may be NULL), as scone_backward_plan
+ *                                    does.  ntok == 0 and U == 0 are valid empty plans.  The result is a scone_bwd_plan:
+ *                                    scone_backward_rows (d_row_ids_out: the ids, int64 ascending; d_grad_rows_out [U, d] fp32:
+ *                                    the rows of the dense gradient that are not zero), scone_backward_row_ids,
+ *                                    scone_backward_counts (K_p: 0 or 1), scone_backward_rows_acc and
+ *                                    scone_backward_plan_destroy take it as they take any other.  scone_backward_apply_lean
+ *                                    returns SCONE_EINVAL for it: its ids are not table rows.  SCONE_EINVAL: a null out, a null
+ *                                    d_idx with ntok > 0, ntok < 0 or ntok >= 2^32, n_ids <= 0 or n_ids >= 2^32 - 1, a handle
+ *                                    with dim == 0 or d % 8 != 0
+ *   scone_backward_default_positions writes to d_pos_out [total_tokens] int32 the position the lookup uses for every p when it is
+ *                                    given d_pos == NULL: p % T for the rectangle (d_cu_seqlens == NULL; n_seqs is ignored), the
+ *                                    matcher's p - cu[s] for scone_embed_varlen's packed batch (d_cu_seqlens [n_seqs + 1]; T is
+ *                                    ignored; n_seqs == 0: a no-op).  With it the wpe gradient of a packed batch, or of any batch
+ *                                    with default positions, is an index plan with n_ids = n_pos.  Stream-ordered, one launch:
+ *                                    it does not synchronise and does not allocate.  SCONE_EINVAL: negative sizes, total_tokens
+ *                                    above 2^31 - 1, a rectangle with T <= 0 or total_tokens % T != 0, a null d_pos_out
+ *   scone_backward_wpe_scratch       the bytes of scratch scone_backward_wpe needs for a rectangle [B, T] at dim d: the
+ *                                    partials of ceil(B / C) chunks per row when B > C, else 0.  No handle, no device work
+ *   scone_backward_wpe               grad_wpe of the rectangle [B, T] with DEFAULT positions: row t of d_grad_wpe_out
+ *                                    [min(T, n_pos), d] fp32 is the sum of g[b * T + t, :] for b ascending, g = d_grad_out
+ *                                    [B * T, d] in grad_dtype.  The references of row t are known by arithmetic, so there is no
+ *                                    plan, no sort, no synchronisation and no allocation: a wave owns (row t, chunk j of C batch
+ *                                    rows), computes its positions, and adds in b order; when B > C the partials go to d_scratch
+ *                                    and a second launch adds them in chunk order.  Its bits are those of
+ *                                    scone_backward_plan_index(n_ids = n_pos) on scone_backward_default_positions followed by
+ *                                    scone_backward_rows, for every row t < n_pos (every such row has B >= 1 references); rows
+ *                                    t >= n_pos do not exist -- their position is out of range in the lookup.  B * T == 0: a
+ *                                    no-op.  The call is stream-ordered: it does not synchronise and allocates nothing; at most
+ *                                    two launches.  d_scratch is scratch of the call (may be NULL when the size is 0).
+ *                                    SCONE_EINVAL: null pointers, a bad grad_dtype, negative B or T, B * T above 2^31 - 1,
+ *                                    n_pos <= 0, a handle with dim == 0 or d % 8 != 0
+ * Left out, and meant to be: the index plan in the form whose counts stay on the device (a scone_bwd_ctx).  A captured step
+ * trains the table only. */
+int scone_backward_plan_index(scone_handle *h, const int32_t *d_idx, int64_t ntok, int64_t n_ids, const int32_t *d_skip,
+                              scone_bwd_plan **out, uint64_t *h_n_rows, uint64_t *h_n_refs, void *stream);
+int scone_backward_default_positions(scone_handle *h, const int32_t *d_cu_seqlens, int32_t n_seqs, int32_t T, int64_t total_tokens,
+                                     int32_t *d_pos_out, void *stream);
+int scone_backward_wpe_scratch(int32_t B, int32_t T, int32_t d, uint64_t *bytes);
+int scone_backward_wpe(scone_handle *h, const void *d_grad_out, int32_t grad_dtype, int32_t B, int32_t T, int64_t n_pos,
+                       float *d_grad_wpe_out, void *d_scratch, void *stream);
+
 /* ---- optimizer hyper-parameters on the device: a captured step with Adam, stochastic rounding, a learning-rate schedule and a
  * dynamic loss scale (new here; torch.optim.Adam(capturable=True) keeps its step count on the device for the same reason).
  * SCONE_ABI_VERSION is unchanged; every other entry point keeps its bits, its refusals and its stream contract.  The section

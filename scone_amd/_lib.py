@@ -162,6 +162,15 @@ def backward_ctx_partial_slots(max_refs: int) -> int:
     return int(out.value)
 
 
+def backward_wpe_scratch(B: int, T: int, d: int) -> int:
+    """``scone_backward_wpe_scratch``: the bytes of scratch ``scone_backward_wpe`` needs for a rectangle ``[B, T]`` at ``d``.
+    Runs without a GPU."""
+    out = _U64(0)
+    if lib().scone_backward_wpe_scratch(int(B), int(T), int(d), C.byref(out)) != OK:
+        raise ValueError("scone_backward_wpe_scratch refused its arguments")
+    return int(out.value)
+
+
 # name -> (restype, argtypes); must list every symbol include/scone_hip.h declares
 SIGNATURES = {
     "scone_abi_version": (C.c_int, []),
@@ -294,6 +303,10 @@ SIGNATURES = {
     "scone_opt_step_dh": (C.c_int, [_P, _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "scone_opt_step_lean_dh": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "scone_grad_ctl_set_dh": (C.c_int, [_P, _P, _I32, _P, C.c_double, _I32, _P, _P]),
+    "scone_backward_plan_index": (C.c_int, [_P, _P, _I64, _I64, _P, C.POINTER(_P), C.POINTER(_U64), C.POINTER(_U64), _P]),
+    "scone_backward_default_positions": (C.c_int, [_P, _P, _I32, _I32, _I64, _P, _P]),
+    "scone_backward_wpe_scratch": (C.c_int, [_I32, _I32, _I32, C.POINTER(_U64)]),
+    "scone_backward_wpe": (C.c_int, [_P, _P, _I32, _I32, _I32, _I64, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

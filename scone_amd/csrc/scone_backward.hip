@@ -357,7 +357,9 @@ int plan_build(scone_handle *h, scone_bwd_plan *pl, const bwd_plan_src &src, uns
     SCONE_HIP(h, hipStreamSynchronize(s));
     return SCONE_OK;
   }
-  const bwd_plan_sizes z = scone_bwd_plan_sizes(h, max_refs);
+  const bwd_plan_sizes z = src.kind == BWD_SRC_INDEX
+                               ? scone_bwd_plan_sizes_ids(max_refs, (unsigned long long)src.n_ids, (unsigned long long)src.n_ids)
+                               : scone_bwd_plan_sizes(h, max_refs);
   const unsigned long long seg_cap = z.seg_cap;
 
   if (!pl->d_kfull) SCONE_HIP(h, hipMalloc(&pl->d_kfull, (size_t)ntok * 4));
@@ -468,14 +470,31 @@ unsigned long long scone_bwd_cand_per_token(const scone_handle *h) {
 }
 
 bwd_plan_sizes scone_bwd_plan_sizes(const scone_handle *h, unsigned long long max_refs) {
+  return scone_bwd_plan_sizes_ids(max_refs, h->cfg.n_rows, h->cfg.row_end - h->cfg.row_begin);
+}
+
+bwd_plan_sizes scone_bwd_plan_sizes_ids(unsigned long long max_refs, unsigned long long n_ids, unsigned long long owned) {
   bwd_plan_sizes z;
-  const unsigned long long owned = h->cfg.row_end - h->cfg.row_begin;
   z.max_refs = max_refs;
   z.seg_cap = max_refs < owned ? max_refs : owned;
   z.chunk_cap = max_refs / SCONE_BWD_CHUNK + z.seg_cap + 1;
   z.multi_cap = max_refs / SCONE_BWD_CHUNK + 1;
-  z.end_bit = bits_for(h->cfg.n_rows + 1);
+  z.end_bit = bits_for(n_ids + 1);
+  z.pad_key = (uint32_t)n_ids;
   return z;
+}
+
+int scone_bwd_scan_u32(scone_handle *h, void *scratch, size_t scratch_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s) {
+  SCONE_HIP(h, rocprim::exclusive_scan(scratch, scratch_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
+  return SCONE_OK;
+}
+
+int scone_bwd_plan_make(scone_handle *h, const bwd_plan_src &src, long long ntok, unsigned long long max_refs, scone_bwd_plan **out,
+                        uint64_t *h_n_rows, uint64_t *h_n_refs, hipStream_t s) {
+  scone_bwd_plan *pl = plan_new(h, ntok);
+  if (!pl) return scone_fail(h, SCONE_ENOMEM, "scone_backward_plan: out of memory");
+  pl->index = src.kind == BWD_SRC_INDEX;
+  return plan_finish(h, pl, plan_build(h, pl, src, max_refs, s), out, h_n_rows, h_n_refs);
 }
 
 int scone_bwd_plan_scratch(scone_handle *h, long long ntok, const bwd_plan_sizes &z, hipStream_t s, size_t *need_out) {
@@ -499,11 +518,13 @@ int scone_bwd_plan_scratch(scone_handle *h, long long ntok, const bwd_plan_sizes
 int scone_bwd_plan_enqueue(scone_handle *h, const bwd_plan_src &src, long long ntok, const bwd_plan_sizes &z, const bwd_plan_bufs &b,
                            hipStream_t s) {
   const unsigned long long n_rows = h->cfg.n_rows, max_refs = z.max_refs, seg_cap = z.seg_cap;
-  const uint32_t pad_key = (uint32_t)n_rows;
+  const uint32_t pad_key = z.pad_key;
   const size_t need = b.scratch_bytes;
   size_t n1;
   // (1) id lists -> K_own / K_full / w per position, the reference offsets, the (row, p) pairs in (p, k) order
-  if (src.kind == BWD_SRC_CSR) {  // counted by the caller
+  if (src.kind == BWD_SRC_INDEX) {
+    SCONE_TRY(scone_bwd_index_pairs(h, src, ntok, b, s));
+  } else if (src.kind == BWD_SRC_CSR) {  // counted by the caller
     n1 = need;
     SCONE_HIP(h, rocprim::exclusive_scan(b.scratch, n1, b.kown, b.ref_off, 0u, (size_t)(ntok + 1), rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL(k_bwd_expand_csr, dim3(blocks_for(ntok)), dim3(BWD_THREADS), 0, s, src.offsets, src.ids, ntok, src.csr_total,

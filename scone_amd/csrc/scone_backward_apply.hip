@@ -375,6 +375,7 @@ extern "C" int scone_backward_apply_lean(scone_handle *h, scone_bwd_plan *plan, 
   SCONE_TRY(opt_need_table(h, who, lean_check(cfg)));
   if (!plan) return scone_refuse(h, SCONE_EINVAL, who, "null plan");
   if (plan->h != h) return scone_refuse(h, SCONE_EINVAL, who, "the plan belongs to another handle");
+  if (plan->index) return scone_refuse(h, SCONE_EINVAL, who, "an index plan's ids are not table rows (scone_backward_plan_index)");
   if (grad_dtype != SCONE_DT_F32 && grad_dtype != SCONE_DT_F16 && grad_dtype != SCONE_DT_BF16)
     return scone_refuse(h, SCONE_EINVAL, who, "bad grad_dtype");
   if (reduce != SCONE_REDUCE_MEAN && reduce != SCONE_REDUCE_SUM) return scone_refuse(h, SCONE_EINVAL, who, "bad reduce");

@@ -39,6 +39,7 @@ struct scone_bwd_plan {
   int device = 0;
   int dim = 0;
   long long ntok = 0;
+  bool index = false;  // an index plan (scone_backward_plan_index): its ids are those of the caller's id space, not table rows
   bwd_meta m = {};
   // kept for the life of the plan
   int32_t *d_kfull = nullptr;     // [ntok] K_p, the full hit count
@@ -53,17 +54,19 @@ struct scone_bwd_plan {
 
 // ---- one plan build, whoever owns its buffers (scone_backward.hip): scone_backward_plan* allocate them per call and read the
 // totals back; a scone_bwd_ctx (scone_backward_dn.hip) holds them at its worst-case sizes and leaves the totals on the device.
-enum { BWD_SRC_RECT = 0, BWD_SRC_PACKED = 1, BWD_SRC_CSR = 2 };
+enum { BWD_SRC_RECT = 0, BWD_SRC_PACKED = 1, BWD_SRC_CSR = 2, BWD_SRC_INDEX = 3 };
 
 struct bwd_plan_src {
   int kind;
-  const int32_t *tok;
+  const int32_t *tok;      // the tokens; the ids idx [ntok] of an index plan
   int32_t B, T;            // rectangle
   const int32_t *cu;       // packed
   int32_t n_seqs;
   const int32_t *offsets;  // CSR
   const int32_t *ids;
   long long csr_total;
+  const int32_t *skip;     // index plan: position p has no reference where skip[p] != 0 (may be null)
+  long long n_ids;         // index plan: the size of its id space
 };
 
 // what a plan of at most max_refs references can need: all host-known
@@ -72,7 +75,8 @@ struct bwd_plan_sizes {
   unsigned long long seg_cap;    // most distinct rows: min(max_refs, owned rows)
   unsigned long long chunk_cap;  // most chunks
   unsigned long long multi_cap;  // most rows with several chunks
-  int end_bit;                   // the sort's key bits: those of n_rows, the pad key
+  int end_bit;                   // the sort's key bits: those of the pad key
+  uint32_t pad_key;              // the size of the plan's id space (n_rows of the table; n_ids of an index plan): behind every id
 };
 
 struct bwd_plan_bufs {
@@ -97,12 +101,21 @@ struct bwd_plan_bufs {
 };
 
 bwd_plan_sizes scone_bwd_plan_sizes(const scone_handle *h, unsigned long long max_refs);
+// the same for any id space: ids in [0, n_ids), of which `owned` can have a reference
+bwd_plan_sizes scone_bwd_plan_sizes_ids(unsigned long long max_refs, unsigned long long n_ids, unsigned long long owned);
 // the bytes the sort and the four scans of a build need at most (host only: no device work)
 int scone_bwd_plan_scratch(scone_handle *h, long long ntok, const bwd_plan_sizes &z, hipStream_t s, size_t *need);
 // enqueues the whole build on s: no allocation but the workspace's (b.ell == null), no synchronisation.  ntok > 0, max_refs > 0.
 // The CSR form's kown / kfull / w are counted by the caller (it needs the owned count first).
 int scone_bwd_plan_enqueue(scone_handle *h, const bwd_plan_src &src, long long ntok, const bwd_plan_sizes &z, const bwd_plan_bufs &b,
                            hipStream_t s);
+// a new plan of `ntok` positions built from `src` (which allocates, and synchronises s once) and handed out, or freed on failure
+int scone_bwd_plan_make(scone_handle *h, const bwd_plan_src &src, long long ntok, unsigned long long max_refs, scone_bwd_plan **out,
+                        uint64_t *h_n_rows, uint64_t *h_n_refs, hipStream_t s);
+// step (1) of a build from BWD_SRC_INDEX (scone_backward_index.hip): K_p / w, the reference offsets, the (id, p) pairs
+int scone_bwd_index_pairs(scone_handle *h, const bwd_plan_src &src, long long ntok, const bwd_plan_bufs &b, hipStream_t s);
+// rocPRIM's exclusive scan of n uint32 with the build's scratch
+int scone_bwd_scan_u32(scone_handle *h, void *scratch, size_t scratch_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
 // references a position can have: max_n (max_n + 1) / 2, or 1 in longest_suffix mode
 unsigned long long scone_bwd_cand_per_token(const scone_handle *h);
 // the largest sort that stays with rocPRIM's merge sort (no kernel with a private segment)

@@ -1472,6 +1472,97 @@ class SconeTable:
                                              C.byref(n_refs), stream)
         return self._make_plan(rc, "scone_backward_plan_csr", plan, ntok, n_rows, n_refs)
 
+    # -- backward of the dense side (wte / wpe) -----------------------------------
+    def backward_plan_index(self, idx: torch.Tensor, n_ids: int, skip: Optional[torch.Tensor] = None) -> BackwardPlan:
+        """``scone_backward_plan_index``: the plan of a dense embedding's gradient -- position ``p`` refers to row ``idx[p]`` of
+        an id space of ``n_ids`` rows (``wte``: the tokens and the vocabulary; ``wpe``: the position ids and ``n_pos``), which
+        has nothing to do with the table's.  ``skip`` (int32, as long as ``idx``): positions with ``skip != 0`` have no
+        reference; so have ids outside ``[0, n_ids)``, silently.  :meth:`BackwardPlan.rows` then returns the ids with a
+        reference and their fp32 gradient rows, summed in the backward's fixed order.  Synchronises the current stream once."""
+        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        ntok = idx.numel()
+        if skip is not None:
+            skip = torch.as_tensor(skip).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+            if skip.numel() != ntok:
+                raise ValueError(f"backward_plan_index: skip must have the {ntok} elements of idx, got {skip.numel()}")
+        plan, n_rows, n_refs = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = L.lib().scone_backward_plan_index(self._h, _ptr(idx) if ntok else None, ntok, int(n_ids),
+                                                   _ptr(skip) if skip is not None and ntok else None, C.byref(plan),
+                                                   C.byref(n_rows), C.byref(n_refs), stream)
+        return self._make_plan(rc, "scone_backward_plan_index", plan, ntok, n_rows, n_refs)
+
+    def default_positions(self, B: Optional[int] = None, T: Optional[int] = None, *, cu_seqlens=None,
+                          total: Optional[int] = None) -> torch.Tensor:
+        """``scone_backward_default_positions``: the position the lookup gives every ``p`` when it is called without
+        ``position_ids``, int32 -- ``[B * T]`` (``p % T``) for ``default_positions(B, T)``, ``[total]`` (``p - cu[s]``) for
+        ``default_positions(cu_seqlens=, total=)``.  No synchronisation with a device ``cu_seqlens``."""
+        if cu_seqlens is None:
+            if B is None or T is None:
+                raise ValueError("default_positions: give (B, T) or cu_seqlens= and total=")
+            n, cu, n_seqs, T = int(B) * int(T), None, int(B), int(T)
+        else:
+            if total is None:
+                raise ValueError("default_positions: a packed batch needs total=")
+            n, T = int(total), 0
+            if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+                if not (cu_seqlens.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+                        and cu_seqlens.numel() >= 1):
+                    raise ValueError("a device cu_seqlens must be a contiguous 1-D int32 tensor [n_seqs + 1]")
+                cu = cu_seqlens
+            else:
+                cu = torch.from_numpy(check_cu_seqlens(cu_seqlens, n)).to(self.device)
+            n_seqs = cu.numel() - 1
+        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_backward_default_positions(self._h, _ptr(cu), n_seqs, T, n, _ptr(out) if n else None,
+                                                          stream.cuda_stream)
+        if rc == L.EINVAL:
+            raise SconeInvalidArgument(f"scone_backward_default_positions: {L.lib().scone_last_error(self._h).decode()} "
+                                       f"[{L.lib().scone_strerror(rc).decode()}]")
+        self._check(rc, "scone_backward_default_positions")
+        if cu is not None and n:
+            cu.record_stream(stream)
+        return out
+
+    def backward_wpe(self, grad_out: torch.Tensor, n_pos: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``scone_backward_wpe``: the gradient of ``wpe`` for a rectangle looked up with default positions -- fp32
+        ``[min(T, n_pos), d]``, row ``t`` the sum of ``grad_out[b, t, :]`` over ``b`` ascending in the backward's fixed order
+        (the bits of :meth:`backward_plan_index` on :meth:`default_positions`).  ``grad_out``: ``[B, T, d]`` fp32 / fp16 / bf16.
+        No plan, no sort, no synchronisation; the scratch of a batch of more than ``backward_chunk()`` sequences is kept on the
+        table and grows only when a larger batch comes."""
+        if grad_out.dim() != 3 or grad_out.shape[-1] != self.dim:
+            raise ValueError(f"grad_out must be [B, T, {self.dim}], got {tuple(grad_out.shape)}")
+        if grad_out.dtype not in _DT:
+            raise ValueError(f"grad_out must be fp32, fp16 or bf16, not {grad_out.dtype}")
+        if int(n_pos) <= 0:
+            raise ValueError("backward_wpe: n_pos must be positive")
+        if not (grad_out.is_cuda and grad_out.device == self.device and grad_out.is_contiguous()):
+            grad_out = grad_out.to(device=self.device).contiguous()
+        B, T = int(grad_out.shape[0]), int(grad_out.shape[1])
+        rows = min(T, int(n_pos)) if B else 0
+        if out is None:
+            out = torch.empty((rows, self.dim), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.device == self.device and out.is_contiguous() and out.dtype == torch.float32
+                  and tuple(out.shape) == (rows, self.dim)):
+            raise ValueError(f"out must be a contiguous fp32 [{rows}, {self.dim}] tensor on {self.device}")
+        need = L.backward_wpe_scratch(B, T, self.dim)
+        scratch = getattr(self, "_wpe_scratch", None)
+        if need and (scratch is None or scratch.numel() < need):
+            scratch = self._wpe_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = L.lib().scone_backward_wpe(self._h, _ptr(grad_out) if B * T else None, _DT[grad_out.dtype], B, T, int(n_pos),
+                                            _ptr(out) if rows else None, _ptr(scratch) if need else None, stream.cuda_stream)
+        self._check(rc, "scone_backward_wpe")
+        if B * T:
+            grad_out.record_stream(stream)                       # it may be a temporary of the caller
+            if need:
+                scratch.record_stream(stream)
+        return out
+
     def _sparse_operand(self, who: str, ids: torch.Tensor, rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(ids, rows)`` of a sparse row gradient, checked and made contiguous on the table's device."""
         if ids.dim() != 1 or ids.dtype != torch.int64:

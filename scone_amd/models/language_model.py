@@ -10,7 +10,8 @@ transformer as ``inputs_embeds`` (language_model.py:234-258) comes from:
   mean, ``+ wte(input_ids)``, ``+ wpe(position_ids)`` -- is one fused pass of the
   HIP kernels (``scone_embed``), the bias-free projection
   (language_model.py:172-176) having been folded into the table offline
-  (:func:`fold_projection`; ``proj(mean(rows)) == mean(proj(rows))``);
+  (:func:`fold_projection`; ``proj(mean(rows)) == mean(proj(rows))``); when ``wte`` / ``wpe`` require grad the same pass is
+  on the autograd tape and their gradients are the library's fixed-order sums (``scone_amd.training``);
 * with explicit ``f_gram_embeddings`` the reference arithmetic is applied as is
   (projection GEMM through rocBLAS, two adds) on the device the tensors live on.
 
@@ -49,6 +50,12 @@ class SconeEmbedding(nn.Module):
             if self.embedding_cache.embedding_dim != self.wte.weight.shape[1]:
                 raise ValueError("fused lookup needs a table in hidden size: fold the projection into it "
                                  "(scone_amd.models.language_model.fold_projection)")
+            if torch.is_grad_enabled() and (self.wte.weight.requires_grad or self.wpe.weight.requires_grad):
+                # fine-tuning: the same call on the tape, wte / wpe trained by the library's deterministic index-plan sums
+                # (the table is not a parameter here, so in cover mode no table plan is built)
+                from scone_amd.training import embed_tokens_dense_grad
+                return embed_tokens_dense_grad(self.embedding_cache, input_ids, wte=self.wte.weight, wpe=self.wpe.weight,
+                                               position_ids=position_ids, out_dtype=self.wte.weight.dtype)
             return self.embedding_cache.embed_tokens(
                 input_ids, reduce="mean", wte=self.wte.weight.detach().contiguous(),
                 wpe=self.wpe.weight.detach().contiguous(), position_ids=position_ids,

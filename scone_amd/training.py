@@ -4,8 +4,9 @@ In the reference the f-gram table is a trained ``nn.Embedding`` (scone/models/f_
 added to the token embeddings (scone/models/language_model.py:239-243).  :class:`TrainableFGramTable` puts the one-launch
 lookup of :class:`~scone_amd.EmbeddingCache` on an autograd tape: the forward is the existing kernel, bit for bit, and the
 backward is the library's deterministic sparse row gradient (include/scone_hip.h, "backward") -- no host synchronise in
-the reduction, no float atomics, the same bits on every run.  The training loop and ``wte`` / ``wpe`` stay the caller's
-torch code, added outside, as language_model.py:239-254 does.  The table's own update is either a stock ``torch.optim``
+the reduction, no float atomics, the same bits on every run.  ``wte`` / ``wpe`` either stay the caller's torch code, added
+outside as language_model.py:239-254 does (``base=``), or are passed to the lookup (``wte=`` / ``wpe=``) and trained through it:
+their gradients are the same fixed-order sums in a second id space (include/scone_hip.h, "backward of the dense side").  The table's own update is either a stock ``torch.optim``
 sparse step followed by :meth:`TrainableFGramTable.commit`, or :class:`FGramOptimizer`: one kernel launch that updates the
 touched master rows, their optimizer state and the served table (include/scone_hip.h, "optimizer step").
 """
@@ -97,70 +98,168 @@ class _StaticGrad:
         module.static_grad = self.ctx.rows(grad_out, reduce, out=(self.ids, self.rows, self.n))
 
 
+def _dense_inputs(who: str, wte, wpe, base, static) -> None:
+    """The refusals of the dense side, before any device work (called outside the autograd function, where the caller's grad
+    mode is still visible)."""
+    if wte is not None and base is not None:
+        raise ValueError(f"{who}: wte= and base= do not go together (base IS the dense term: pass one of them)")
+    if static is not None and torch.is_grad_enabled() and any(w is not None and w.requires_grad for w in (wte, wpe)):
+        raise ValueError(f"{who}: static_rows= trains the table only -- a wte / wpe that requires grad needs the index plan with "
+                         "its counts on the device (the _dn form of scone_backward_plan_index), which does not exist yet; "
+                         "pass them detached, or build the module without static_rows=")
+
+
+def _dense_grads(table, tok, cu, position_ids, grad_out, wte, wpe, skip, sparse_wte):
+    """``(grad_wte, grad_wpe)`` of ``out = (wte[tok] + fg) + wpe[pos]`` (include/scone_hip.h, "backward of the dense side"): each
+    an index plan summed in the backward's fixed order -- no float atomics, the same bits on every run.  ``wte`` / ``wpe``: the
+    tensor whose gradient is wanted, or ``None``.  ``skip``: the table plan's hit counts in longest_suffix mode (a matched f-gram
+    replaced the token term), else ``None``.  ``grad_wpe`` is never masked: the position term is added in both modes."""
+    grad_wte = grad_wpe = None
+    d = table.dim
+    if wte is not None:
+        with table.backward_plan_index(tok.reshape(-1), wte.shape[0], skip=skip) as plan:
+            ids, rows = plan.rows(grad_out, "sum")
+        rows = rows.to(wte.dtype)
+        if sparse_wte:
+            grad_wte = torch.sparse_coo_tensor(ids[None], rows, tuple(wte.shape), is_coalesced=True)
+        else:                                           # distinct ids: index_copy_ is deterministic
+            grad_wte = torch.zeros(tuple(wte.shape), dtype=wte.dtype, device=rows.device).index_copy_(0, ids, rows)
+    if wpe is not None:
+        n_pos = wpe.shape[0]
+        grad_wpe = torch.zeros((n_pos, d), dtype=wpe.dtype, device=grad_out.device)
+        if cu is None and position_ids is None:         # the rectangle with default positions: no plan
+            g3 = grad_out if grad_out.dim() == 3 else grad_out.reshape(1, -1, d)
+            rows = table.backward_wpe(g3, n_pos)
+            grad_wpe[:rows.shape[0]].copy_(rows)
+        else:
+            ntok = grad_out.numel() // d
+            if position_ids is not None:
+                pos = torch.as_tensor(position_ids).to(device=table.device, dtype=torch.int32)
+                pos = pos.reshape(-1) if cu is not None else pos.expand(*grad_out.shape[:-1]).reshape(-1)
+            else:
+                pos = table.default_positions(cu_seqlens=cu, total=ntok)
+            with table.backward_plan_index(pos, n_pos) as plan:
+                ids, rows = plan.rows(grad_out, "sum")
+            grad_wpe.index_copy_(0, ids, rows.to(wpe.dtype))
+    return grad_wte, grad_wpe
+
+
+def _hand_over_wte_grad(wte: torch.Tensor, grad):
+    """A SPARSE ``grad_wte`` is set on a leaf ``wte`` here, not returned: autograd's accumulation re-creates a sparse gradient
+    without its coalesced flag (as for the table's own gradient).  Returns what the backward still has to return."""
+    if grad is None or not grad.is_sparse or not wte.is_leaf:
+        return grad
+    if wte.grad is None:
+        wte.grad = grad
+    elif wte.grad.is_sparse:
+        wte.grad = _add_coalesced(wte.grad, grad._indices()[0], grad._values())
+    else:
+        wte.grad.index_add_(0, grad._indices()[0], grad._values())        # onto a dense gradient: distinct ids, one add per element
+    return None
+
+
 class _Lookup(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weight, base, module, input_ids, cu_seqlens, reduce, out_dtype):
+    def forward(ctx, weight, base, module, input_ids, cu_seqlens, reduce, out_dtype, wte=None, wpe=None, position_ids=None):
         cache = module.cache
         tok = torch.as_tensor(input_ids)
+        dense = {}
+        if wte is not None or wpe is not None or position_ids is not None:
+            dense = dict(wpe=None if wpe is None else wpe.detach().contiguous(), position_ids=position_ids)
         if base is not None and cache.lookup_mode == "longest_suffix":
             # the paper's lookup onto a dense base (a matched f-gram REPLACES the base row) is the table's call
             table = cache.to_device()
             if cu_seqlens is None:
-                out = table.embed_base(tok, base, reduce=reduce, out_dtype=out_dtype)
+                out = table.embed_base(tok, base, reduce=reduce, out_dtype=out_dtype, **dense)
             else:
-                out = table.embed_base_varlen(tok, cu_seqlens, base, reduce=reduce, out_dtype=out_dtype)
+                out = table.embed_base_varlen(tok, cu_seqlens, base, reduce=reduce, out_dtype=out_dtype, **dense)
         else:
-            out = cache.embed_tokens(tok, reduce=reduce, base=base, cu_seqlens=cu_seqlens, out_dtype=out_dtype)
+            if wte is not None:
+                dense["wte"] = wte.detach().contiguous()
+            out = cache.embed_tokens(tok, reduce=reduce, base=base, cu_seqlens=cu_seqlens, out_dtype=out_dtype, **dense)
         ctx.module, ctx.tok, ctx.cu, ctx.reduce = module, tok, cu_seqlens, reduce
         ctx.base_dtype = None if base is None else base.dtype
         ctx.base_shape = None if base is None else base.shape
+        ctx.wte, ctx.wpe, ctx.position_ids = wte, wpe, position_ids
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         module = ctx.module
         table = module.cache.to_device()
-        grad_weight = grad_base = None
+        grad_weight = grad_base = grad_wte = grad_wpe = None
         grad_out = grad_out.contiguous()
+        need_wte = ctx.wte is not None and ctx.needs_input_grad[7]
+        need_wpe = ctx.wpe is not None and ctx.needs_input_grad[8]
         static = getattr(module, "_static", None)
         if static is not None:                                # static_rows=: the counts stay on the device
-            static.check(module, ctx.base_dtype)
+            static.check(module, ctx.base_dtype)              # (a trainable wte / wpe was refused by the forward)
             if ctx.needs_input_grad[0]:
                 static.backward(module, ctx.tok, ctx.cu, grad_out, ctx.reduce)
             if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
                 grad_base = grad_out.to(ctx.base_dtype).reshape(ctx.base_shape)
-            return grad_weight, grad_base, None, None, None, None, None
+            return grad_weight, grad_base, None, None, None, None, None, None, None, None
         fused = getattr(module, "_fused_opt", None)           # an FGramOptimizer(fused_backward=True): the update happens here
-        with table.backward_plan(ctx.tok, ctx.cu) as plan:
-            if ctx.needs_input_grad[0] and fused is not None:
-                fused._apply_backward(plan, grad_out, ctx.reduce)
-            elif ctx.needs_input_grad[0]:
-                old = module._mergeable_grad()
-                if old is not None:
-                    # a gradient is already there: the library adds this batch's rows to it, and they are never stored
-                    module._set_merged(plan.row_ids(), *plan.rows(grad_out, ctx.reduce, accumulate=old))
-                else:
-                    row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
-                    # set on the module, not returned: autograd's accumulation re-creates a sparse gradient without its
-                    # coalesced flag
-                    module._accumulate(row_ids, grad_rows)
-            if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
-                grad_base = grad_out
-                if module.cache.lookup_mode == "longest_suffix":     # a matched f-gram replaced the base row
-                    keep = (plan.counts() == 0).reshape(*grad_out.shape[:-1], 1)
-                    grad_base = grad_out * keep
-                grad_base = grad_base.to(ctx.base_dtype).reshape(ctx.base_shape)
-        # (the plan is closed while its kernels may still run: freeing device memory waits for the device)
-        return grad_weight, grad_base, None, None, None, None, None
+        suffix = module.cache.lookup_mode == "longest_suffix"
+        need_base = ctx.base_dtype is not None and ctx.needs_input_grad[1]
+        skip = None
+        if ctx.needs_input_grad[0] or (suffix and (need_base or need_wte)):   # else the table's plan has nothing to give
+            with table.backward_plan(ctx.tok, ctx.cu) as plan:
+                if ctx.needs_input_grad[0] and fused is not None:
+                    fused._apply_backward(plan, grad_out, ctx.reduce)
+                elif ctx.needs_input_grad[0]:
+                    old = module._mergeable_grad()
+                    if old is not None:
+                        # a gradient is already there: the library adds this batch's rows to it, and they are never stored
+                        module._set_merged(plan.row_ids(), *plan.rows(grad_out, ctx.reduce, accumulate=old))
+                    else:
+                        row_ids, grad_rows = plan.rows(grad_out, ctx.reduce)
+                        # set on the module, not returned: autograd's accumulation re-creates a sparse gradient without its
+                        # coalesced flag
+                        module._accumulate(row_ids, grad_rows)
+                if suffix and (need_base or need_wte):        # a matched f-gram replaced the base row / the token term
+                    skip = plan.counts()
+            # (the plan is closed while its kernels may still run: freeing device memory waits for the device)
+        if need_base:
+            grad_base = grad_out
+            if suffix:
+                grad_base = grad_out * (skip == 0).reshape(*grad_out.shape[:-1], 1)
+            grad_base = grad_base.to(ctx.base_dtype).reshape(ctx.base_shape)
+        if need_wte or need_wpe:
+            grad_wte, grad_wpe = _dense_grads(table, ctx.tok, ctx.cu, ctx.position_ids, grad_out, ctx.wte if need_wte else None,
+                                              ctx.wpe if need_wpe else None, skip, getattr(module, "sparse_wte_grad", False))
+            if need_wte:
+                grad_wte = _hand_over_wte_grad(ctx.wte, grad_wte)
+        return grad_weight, grad_base, None, None, None, None, None, grad_wte, grad_wpe, None
+
+
+class _DenseSide:
+    """What :class:`_Lookup` asks of a module, for a lookup whose table is NOT trained (``SconeEmbedding`` with a cache)."""
+
+    def __init__(self, cache, sparse_wte_grad: bool = False) -> None:
+        self.cache, self.sparse_wte_grad = cache, bool(sparse_wte_grad)
+
+
+def embed_tokens_dense_grad(cache: EmbeddingCache, input_ids: torch.Tensor, *, wte: Optional[torch.Tensor] = None,
+                            wpe: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, cu_seqlens=None,
+                            reduce: str = "mean", out_dtype: Optional[torch.dtype] = None,
+                            sparse_wte_grad: bool = False) -> torch.Tensor:
+    """``cache.embed_tokens(input_ids, wte=, wpe=, ...)`` -- the same call, the same bits -- differentiable in ``wte`` and ``wpe``
+    while the table stays fixed: their gradients are the library's deterministic index-plan sums (``_dense_grads``).  In cover
+    mode no table plan is built."""
+    return _Lookup.apply(None, None, _DenseSide(cache, sparse_wte_grad), input_ids, cu_seqlens, reduce, out_dtype, wte, wpe,
+                         position_ids)
 
 
 class _LiveLookup(torch.autograd.Function):
     """:meth:`LiveFGramBatch.embed` on the tape: the forward is ``scone_embed_rows`` on the batch's live rows, the backward
-    the plan's deterministic row gradient -- ``[U, d]``, row ``u`` belonging to ``row_ids[u]``: the gradient of ``rows``."""
+    the plan's deterministic row gradient -- ``[U, d]``, row ``u`` belonging to ``row_ids[u]``: the gradient of ``rows`` -- and
+    the index-plan gradients of ``wte`` / ``wpe``."""
 
     @staticmethod
-    def forward(ctx, rows, base, batch, wte, wpe, position_ids, reduce, out_dtype, out):
-        y = batch.table.embed_rows(batch.input_ids, batch.plan.row_ids(), rows.detach(), cu_seqlens=batch.cu_seqlens, wte=wte, wpe=wpe,
+    def forward(ctx, rows, base, batch, wte, wpe, position_ids, reduce, out_dtype, out, sparse_wte):
+        y = batch.table.embed_rows(batch.input_ids, batch.plan.row_ids(), rows.detach(), cu_seqlens=batch.cu_seqlens,
+                                   wte=None if wte is None else wte.detach(), wpe=None if wpe is None else wpe.detach(),
                                    base=None if base is None else base.detach(), pos=position_ids, reduce=reduce,
                                    out_dtype=out_dtype, out=out)
         if out is not None:
@@ -168,21 +267,31 @@ class _LiveLookup(torch.autograd.Function):
         ctx.batch, ctx.reduce, ctx.rows_dtype = batch, reduce, rows.dtype
         ctx.base_dtype = None if base is None else base.dtype
         ctx.base_shape = None if base is None else base.shape
+        ctx.wte, ctx.wpe, ctx.position_ids, ctx.sparse_wte = wte, wpe, position_ids, sparse_wte
         return y
 
     @staticmethod
     def backward(ctx, grad_out):
         batch = ctx.batch
-        grad_rows = grad_base = None
+        grad_rows = grad_base = grad_wte = grad_wpe = None
         grad_out = grad_out.contiguous()
+        suffix = batch.cache.lookup_mode == "longest_suffix"
+        need_wte = ctx.wte is not None and ctx.needs_input_grad[3]
+        need_wpe = ctx.wpe is not None and ctx.needs_input_grad[4]
         if ctx.needs_input_grad[0]:
             grad_rows = batch.plan.rows(grad_out, ctx.reduce)[1].to(ctx.rows_dtype)
         if ctx.base_dtype is not None and ctx.needs_input_grad[1]:
             grad_base = grad_out                                     # as _Lookup returns it
-            if batch.cache.lookup_mode == "longest_suffix":          # a matched f-gram replaced the base row
+            if suffix:                                               # a matched f-gram replaced the base row
                 grad_base = grad_out * (batch.plan.counts() == 0).reshape(*grad_out.shape[:-1], 1)
             grad_base = grad_base.to(ctx.base_dtype).reshape(ctx.base_shape)
-        return grad_rows, grad_base, None, None, None, None, None, None, None
+        if need_wte or need_wpe:
+            skip = batch.plan.counts() if suffix and need_wte else None
+            grad_wte, grad_wpe = _dense_grads(batch.table, batch.input_ids, batch.cu_seqlens, ctx.position_ids, grad_out,
+                                              ctx.wte if need_wte else None, ctx.wpe if need_wpe else None, skip, ctx.sparse_wte)
+            if need_wte:
+                grad_wte = _hand_over_wte_grad(ctx.wte, grad_wte)
+        return grad_rows, grad_base, None, grad_wte, grad_wpe, None, None, None, None, None
 
 
 class LiveFGramBatch:
@@ -226,15 +335,20 @@ class LiveFGramBatch:
 
     def embed(self, rows: torch.Tensor, *, wte: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
               base: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, reduce: str = "mean",
-              out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+              sparse_wte_grad: bool = False) -> torch.Tensor:
         """``out = (base | wte[input_ids]) + reduce_k rows[slot of f_gram_k] + wpe[position_ids]`` -- :meth:`EmbeddingCache.embed_tokens`
         with the f-gram rows taken from ``rows [U, d]`` (fp32 / fp16 / bf16; row ``u`` is the row of ``row_ids[u]``), bit
         for bit what a table of that type holding them would give.  The gradient of ``rows`` is the library's deterministic
         sparse row gradient (``[U, d]``, cast to ``rows.dtype``); the gradient of ``base`` is ``grad_out`` (``lookup_mode="cover"``)
-        or ``grad_out * (K == 0)`` (``"longest_suffix"``: a matched f-gram replaced the base row).  ``wte`` / ``wpe`` get NO
-        gradient: when they train, pass ``base=wte(input_ids)`` and add the position embeddings outside.  May be called more
-        than once per batch."""
-        return _LiveLookup.apply(rows, base, self, wte, wpe, position_ids, reduce, out_dtype, out)
+        or ``grad_out * (K == 0)`` (``"longest_suffix"``: a matched f-gram replaced the base row).  A ``wte`` / ``wpe``
+        that requires grad is trained through the same call (include/scone_hip.h, "backward of the dense side"): its gradient
+        is dense, in its own dtype, summed in the backward's fixed order without float atomics -- ``grad_wte`` over the tokens
+        (in ``"longest_suffix"`` mode only where no f-gram matched), ``grad_wpe`` over ``position_ids`` or the lookup's default
+        positions, never masked; ``sparse_wte_grad=True`` hands ``grad_wte`` over as a coalesced ``torch.sparse_coo_tensor``.
+        ``wte=`` together with ``base=`` is refused.  May be called more than once per batch."""
+        _dense_inputs("LiveFGramBatch.embed", wte, wpe, base, None)
+        return _LiveLookup.apply(rows, base, self, wte, wpe, position_ids, reduce, out_dtype, out, bool(sparse_wte_grad))
 
     def store(self, rows: torch.Tensor) -> None:
         """Write the batch's rows into the served table at ``row_ids``, whatever its format (``store_f32``)."""
@@ -258,6 +372,10 @@ class TrainableFGramTable(nn.Module):
     optimiser that takes sparse gradients: ``SGD``, ``SparseAdam``, ``Adagrad`` -- or :class:`FGramOptimizer`, which updates
     the served table in the same launch), and returns ``grad_base = grad_out``
     (cover mode) or ``grad_out * (K == 0)`` (longest suffix: a matched f-gram replaced the base row).
+    ``forward(ids, wte=, wpe=, position_ids=)`` is ``embed_tokens(wte=, wpe=)``, bit for bit; a ``wte`` / ``wpe`` that requires
+    grad gets a dense gradient in its own dtype from the library's index plans (deterministic, no float atomics; dense because
+    GPT-2 ties ``wte`` to ``lm_head``, whose gradient is dense) -- ``sparse_wte_grad=True``: a coalesced sparse ``wte.grad``, set
+    on the leaf as the table's is.  ``wte=`` with ``base=`` is refused, and so is a trainable ``wte`` / ``wpe`` in static mode.
     :meth:`commit` re-stores the rows touched since the last commit into the served table, after which it equals a table built
     from the updated weights.  The cache's host copy of the rows, if it keeps one, is not updated: it is the table at
     ingestion time.
@@ -269,8 +387,9 @@ class TrainableFGramTable(nn.Module):
     than ``cap`` rows writes nothing and the step changes nothing (``opt.rows_overflowed()``)."""
 
     def __init__(self, cache: EmbeddingCache, weight: torch.Tensor, static_rows: Optional[int] = None,
-                 max_tokens: Optional[int] = None) -> None:
+                 max_tokens: Optional[int] = None, sparse_wte_grad: bool = False) -> None:
         super().__init__()
+        self.sparse_wte_grad = bool(sparse_wte_grad)
         table = cache.to_device()
         if not isinstance(weight, nn.Parameter):
             weight = nn.Parameter(torch.as_tensor(weight).to(device=table.device, dtype=torch.float32).contiguous())
@@ -283,8 +402,10 @@ class TrainableFGramTable(nn.Module):
         self.static_grad = None         # static mode: (ids, rows, n) after a backward
 
     def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
-                out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-        return _Lookup.apply(self.weight, base, self, input_ids, cu_seqlens, reduce, out_dtype)
+                out_dtype: Optional[torch.dtype] = None, wte: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
+                position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        _dense_inputs("TrainableFGramTable", wte, wpe, base, self._static)
+        return _Lookup.apply(self.weight, base, self, input_ids, cu_seqlens, reduce, out_dtype, wte, wpe, position_ids)
 
     def _mergeable_grad(self):
         """``(row_ids, grad_rows)`` of ``weight.grad`` if the library can add to it (``SconeTable.grad_merge``: coalesced, fp32,
@@ -330,8 +451,10 @@ class InPlaceFGramTable(nn.Module):
     ``static_rows=cap, max_tokens=``: static mode, as on :class:`TrainableFGramTable` -- the backward sets ``static_grad =
     (ids, rows, n)`` with the count on the device, and ``grad`` stays ``None``."""
 
-    def __init__(self, cache: EmbeddingCache, static_rows: Optional[int] = None, max_tokens: Optional[int] = None) -> None:
+    def __init__(self, cache: EmbeddingCache, static_rows: Optional[int] = None, max_tokens: Optional[int] = None,
+                 sparse_wte_grad: bool = False) -> None:
         super().__init__()
+        self.sparse_wte_grad = bool(sparse_wte_grad)
         table = cache.to_device()
         self.cache = cache
         self.shape = (table.n_rows, table.dim)
@@ -342,8 +465,10 @@ class InPlaceFGramTable(nn.Module):
         self.static_grad = None         # static mode: (ids, rows, n) after a backward
 
     def forward(self, input_ids: torch.Tensor, *, base: Optional[torch.Tensor] = None, cu_seqlens=None, reduce: str = "mean",
-                out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-        return _Lookup.apply(self.anchor, base, self, input_ids, cu_seqlens, reduce, out_dtype)
+                out_dtype: Optional[torch.dtype] = None, wte: Optional[torch.Tensor] = None, wpe: Optional[torch.Tensor] = None,
+                position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        _dense_inputs("InPlaceFGramTable", wte, wpe, base, self._static)
+        return _Lookup.apply(self.anchor, base, self, input_ids, cu_seqlens, reduce, out_dtype, wte, wpe, position_ids)
 
     def _mergeable_grad(self):
         """``grad`` if the library can add to it (fp32 rows and int64 ids on the table's device), else ``None``."""
